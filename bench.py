@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the DeepSEE G+D training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,10 @@ batch that is already resident in HBM.  Default workload: independent 8x 32->256
 GPU, fp32 (BASELINE.json configs[1]; weak scaling: the per-GPU batch is fixed as N grows).  `--config` selects the
 other BASELINE configurations (guided_8x_256 = configs[3], independent_32x_512 = configs[4]) for separate lines.
 `python bench.py --gpus N` without a launcher starts the N ranks itself.  Rank 0 prints ONE JSON line.
+
+`--dump-outputs DIR` writes what the LAST timed step handed its caller (rank 0): the generated image as DIR/generated.npy and
+every loss term as DIR/loss_<term>.npy, float32 (see dump_outputs).  Weights, batch and noise are seeded, so two builds run with
+the same arguments can be compared file for file.
 
 Extra objects on the line:
   roofline     — the dominant kernel (by summed time in a step), measured live with HIP events on the launch
@@ -293,6 +297,26 @@ def dp_report(tm, step, fence, world, rank, n, dev, elapsed_local, elapsed, step
     }
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as <path>/<name>.npy (float32 / float64), at most `limit` bytes in all.  Arrays are written
+    smallest first; one that does not fit the bytes left is replaced by a fixed sample of its elements (flattened, indices from
+    numpy's default_rng(0) without replacement, ascending), the same sample in every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = limit - 128 * len(arrays)             # (the .npy header of a file of this kind)
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].nbytes):
+        a = np.asarray(a, order="C")
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.nbytes > left:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def plan_overrides(pairs):
     """--plan FIELD=VALUE ...: values are Python literals, fields those of deepsee_amd.plan.KernelPlan."""
     import ast
@@ -332,7 +356,11 @@ def main():
                     help="--gpus N > 1: the collectives through torch.distributed (RCCL backend) or through dsee_comm_* of the C ABI")
     ap.add_argument("--plan", nargs="*", default=[], metavar="FIELD=VALUE",
                     help="KernelPlan fields of the model (deepsee_amd/plan.py), e.g. --plan fused_norm=False (A/B runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the generated image and the losses of the last timed step as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
 
@@ -397,6 +425,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:
+        # outside the timed region, before any later step: the generated image lives in a buffer the next replay overwrites
+        outs = {"generated": tm.get_latest_generated().detach().float().cpu().numpy()}
+        outs.update(("loss_" + k, v.detach().float().cpu().numpy()) for k, v in tm.get_latest_losses().items())
+        dump_outputs(args.dump_outputs, outs)
 
     # ---- one extra instrumented step: per-launch HIP events around every MFMA kernel and the fused SPADE kernel
     from deepsee_amd import lib as _L

@@ -214,8 +214,10 @@ def test_update_learning_rate_matches_reference_schedule():
 
 
 def _dp_worker(rank, world, port, q):
+    # DSEE_ONE_DEVICE: on a box with a GPU, init_distributed binds every rank to cuda:0 (a one-GPU box has no cuda:1); the
+    # tensors of these workers stay on the host either way
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank))
+                      LOCAL_RANK=str(rank), DSEE_ONE_DEVICE="1")
     sys.path.insert(0, ROOT)
     import random
     import torch.distributed as dist
@@ -261,7 +263,7 @@ def _spawn(fn, world=2, timeout=180):
 
 def _init_gloo(rank, world, port):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
-                      LOCAL_RANK=str(rank))
+                      LOCAL_RANK=str(rank), DSEE_ONE_DEVICE="1")      # (see _dp_worker)
     sys.path.insert(0, ROOT)
     from deepsee_amd import parallel
     r, _, w = parallel.init_distributed(backend="gloo")
