@@ -30,8 +30,9 @@ struct ConvArgs {
   float* out;          // [M][Cout]
   // modulate epilogue (SPADE / SEAN / PureSEAN)
   const float* mx;     // [M][C] tensor being normalised
-  const float* mean;   // [C]
+  const float* mean;   // [C], or [N][C] with stat_ld = C (InstanceNorm: one row per image of stat_px output pixels)
   const float* invstd; // [C]
+  int stat_ld, stat_px;
   float* scale_out;    // [M][C] saved for backward
   float add_one;
   int C;               // channels of mx / out in modulate mode
@@ -109,7 +110,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[M
           const long row = row_of(i, r);
           if (row >= 0) {
             const size_t o = (size_t)row * a.C + c;
-            const float xh = (a.mx[o] - mu) * is;
+            float xh;
+            if (a.stat_ld) {
+              const size_t so = (size_t)((unsigned)row / (unsigned)a.stat_px) * a.stat_ld + c;
+              xh = (a.mx[o] - a.mean[so]) * a.invstd[so];
+            } else {
+              xh = (a.mx[o] - mu) * is;
+            }
             const float sc = acc[i][0][r] + bg + a.add_one;
             const float v = xh * sc + (acc[i][1][r] + bb);
             a.scale_out[o] = sc;
@@ -1660,6 +1667,14 @@ int dsee_conv2d_modulate_fwd(const dsee_conv_geom* g, const float* in, const flo
                              const float* style_table, int shared_cin, const float* bias_packed, const float* x,
                              const float* mean, const float* invstd, float* out_h, float* out_scale, int C,
                              float add_one, float slope, hipStream_t st) {
+  return dsee_conv2d_modulate_fwd_sg(g, in, w_packed, style_table, shared_cin, bias_packed, x, mean, invstd, out_h, out_scale,
+                                     C, 1, add_one, slope, st);
+}
+
+int dsee_conv2d_modulate_fwd_sg(const dsee_conv_geom* g, const float* in, const float* w_packed,
+                                const float* style_table, int shared_cin, const float* bias_packed, const float* x,
+                                const float* mean, const float* invstd, float* out_h, float* out_scale, int C,
+                                int stat_groups, float add_one, float slope, hipStream_t st) {
   ConvArgs a = {};
   int rc = fill_geom(a, g);
   if (rc) return rc;
@@ -1667,6 +1682,9 @@ int dsee_conv2d_modulate_fwd(const dsee_conv_geom* g, const float* in, const flo
   DSEE_CHECK_ARG(g->Cout >= (C + 63) / 64 * 128);  // packed gamma/beta rows
   a.in = in; a.w = w_packed; a.bias = bias_packed; a.out = out_h; a.mx = x; a.mean = mean; a.invstd = invstd;
   a.scale_out = out_scale; a.add_one = add_one; a.C = C; a.slope = slope;
+  DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == g->N);
+  a.stat_ld = stat_groups == 1 ? 0 : C;
+  a.stat_px = g->Ho * g->Wo;
   if (style_table) {
     // the last 32 input channels are the one-hot label (19 padded to 32); their weights are per image
     DSEE_CHECK_ARG(g->korder == 1 && shared_cin % 32 == 0 && shared_cin + 32 == g->Cin);

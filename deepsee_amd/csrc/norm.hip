@@ -457,6 +457,8 @@ __device__ __forceinline__ void store_ata_rows_pk(const f32x4 (&tmp)[6][4], unsi
 // weight / table gradient AND (adjoint form) of the embedding's data gradient; the [M][2C] tensor dgb and the separate
 // A . A^T pass over it never exist.  Thread = (4x4 tile, channel quad); per-channel sums as in norm_bwd_reduce_kernel<1>
 // (one partial row per block, folded in block order by sums_finalize_kernel).  Needs 256 % (C/4) == 0.
+// InstanceNorm (gridDim.y = N statistics groups): block row blockIdx.y walks the tiles of image blockIdx.y only and reads
+// that image's row of mean / invstd; its partial rows are part[blockIdx.y * gridDim.x + blockIdx.x] (image-major).
 __global__ __launch_bounds__(256) void norm_bwd_reduce_wino_kernel(
     const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x,
     const float* __restrict__ scale, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -465,16 +467,17 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_wino_kernel(
   __shared__ f32x4 red[4 * 256];
   float vmax = 0.f;
   const int C4 = C / 4, th = H / 4, tw = W / 4;
-  const long T = (long)N * th * tw, total = T * C4;
+  const long T = (long)N * th * tw, tpg = (long)((unsigned)T / gridDim.y), total = tpg * C4, t0 = (long)blockIdx.y * tpg;
   const int q = threadIdx.x % C4, c0 = q * 4;
-  const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c0), is = *reinterpret_cast<const f32x4*>(invstd + c0);
+  const size_t so = (size_t)blockIdx.y * C + c0;       // (this group's statistics row)
+  const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + so), is = *reinterpret_cast<const f32x4*>(invstd + so);
   const int pcol = (c0 >> 6) * 128 + ((c0 >> 5) & 1) * 64 + (c0 & 31);
   f32x4 acc[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) acc[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     // (32-bit divisions: item counts fit, the ISA has no integer divide -- dsee_common.h)
-    const long t = (long)((unsigned)i / (unsigned)C4);  // (i % C4 == q: gridDim.x * 256 is a multiple of C4)
+    const long t = t0 + (long)((unsigned)i / (unsigned)C4);  // (i % C4 == q: gridDim.x * 256 is a multiple of C4)
     const unsigned r_ = (unsigned)t / (unsigned)tw, n_ = r_ / (unsigned)th;
     const int tx = (int)((unsigned)t - r_ * (unsigned)tw), ty = (int)(r_ - n_ * (unsigned)th), n = (int)n_;
     f32x4 gg[4][4], gx[4][4];
@@ -511,7 +514,7 @@ __global__ __launch_bounds__(256) void norm_bwd_reduce_wino_kernel(
     for (int k = 0; k < 4; ++k) {
       f32x4 v = red[(k * ns) * C4 + q];
       for (int j = 1; j < ns; ++j) v += red[(k * ns + j) * C4 + q];
-      *reinterpret_cast<f32x4*>(part + ((size_t)blockIdx.x * 4 + k) * C + c0) = v;
+      *reinterpret_cast<f32x4*>(part + (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 + k) * C + c0) = v;
     }
   }
 }
@@ -645,6 +648,30 @@ __global__ __launch_bounds__(256) void sums_finalize_kernel(const float* __restr
   if (ok) {
     const int c = i % g.C, grp = (i / g.C) % g.groups, k = i / (g.C * g.groups);
     for (int ch = lane; ch < g.chunks; ch += 32) v += part[((size_t)(grp * g.chunks + ch) * K + k) * g.C + c];
+  }
+  sv[lane][cl] = v;
+  __syncthreads();
+  if (lane == 0 && ok) {
+    for (int l = 1; l < 32; ++l) v += sv[l][cl];
+    sums[i] = v;
+  }
+}
+
+// InstanceNorm form of sums_finalize_kernel for the modulate backward (K = 4, partial rows [G * chunks][4][C], image-major):
+// sums [2G + 2][C] = [2][G][C] (sum d, sum d*xhat per image) then [2][C] (sum g*xhat, sum g over the whole batch, folded in
+// row order).  The same fixed lane-strided fold as sums_finalize_kernel.
+__global__ __launch_bounds__(256) void sums_finalize_sg_kernel(const float* __restrict__ part, float* __restrict__ sums,
+                                                               int chunks, int G, int C) {
+  __shared__ float sv[32][8];
+  const int cl = threadIdx.x & 7, lane = threadIdx.x >> 3;
+  const int i = blockIdx.x * 8 + cl;
+  const bool ok = i < (2 * G + 2) * C;
+  float v = 0.f;
+  if (ok) {
+    const int c = i % C, y = i / C;
+    const int k = y < 2 * G ? y / G : y - 2 * G + 2;
+    const int r0 = y < 2 * G ? (y % G) * chunks : 0, r1 = y < 2 * G ? r0 + chunks : G * chunks;
+    for (int r = r0 + lane; r < r1; r += 32) v += part[((size_t)r * 4 + k) * C + c];
   }
   sv[lane][cl] = v;
   __syncthreads();
@@ -845,13 +872,24 @@ int dsee_norm_act_bwd_amax(const float* dy, const float* y, const float* x, cons
 int dsee_modulate_bwd_reduce(const float* dh, const float* h, const float* x, const float* scale, const float* mean,
                              const float* invstd, float* dgb, int dgb_ld, float* sums, int N, int HW, int C, float slope,
                              float* workspace, hipStream_t st) {
+  return dsee_modulate_bwd_reduce_sg(dh, h, x, scale, mean, invstd, dgb, dgb_ld, sums, N, HW, C, 1, slope, workspace, st);
+}
+
+int dsee_modulate_bwd_reduce_sg(const float* dh, const float* h, const float* x, const float* scale, const float* mean,
+                                const float* invstd, float* dgb, int dgb_ld, float* sums, int N, int HW, int C,
+                                int stat_groups, float slope, float* workspace, hipStream_t st) {
   DSEE_CHECK_ARG(dh && h && x && scale && mean && invstd && dgb && sums && workspace);
   DSEE_CHECK_ARG(C % 4 == 0 && C <= 1024 && dgb_ld >= (C + 63) / 64 * 128);
-  RedGeom g = make_geom(N, HW, C, 1);
-  norm_bwd_reduce_kernel<1><<<dim3(g.chunks, 1), 256, 0, st>>>(dh, h, x, scale, mean, invstd, dgb, dgb_ld, workspace, g,
-                                                                DSEE_ACT_LRELU, slope);
+  DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == N);
+  RedGeom g = make_geom(N, HW, C, stat_groups);
+  norm_bwd_reduce_kernel<1><<<dim3(g.chunks, stat_groups), 256, 0, st>>>(dh, h, x, scale, mean, invstd, dgb, dgb_ld,
+                                                                          workspace, g, DSEE_ACT_LRELU, slope);
   DSEE_LAUNCH_CHECK();
-  sums_finalize_kernel<<<dsee_cdiv((long)4 * C, 8), 256, 0, st>>>(workspace, sums, 4, g);
+  if (stat_groups == 1)
+    sums_finalize_kernel<<<dsee_cdiv((long)4 * C, 8), 256, 0, st>>>(workspace, sums, 4, g);
+  else
+    sums_finalize_sg_kernel<<<dsee_cdiv((long)(2 * stat_groups + 2) * C, 8), 256, 0, st>>>(workspace, sums, g.chunks,
+                                                                                            stat_groups, C);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }
@@ -860,30 +898,51 @@ int dsee_modulate_bwd_reduce(const float* dh, const float* h, const float* x, co
  * dM [36][T][rows] = A (g*xhat | g) A^T in the packed column order (T = N*(H/4)*(W/4), rows = 2C) -- what
  * dsee_wino43_dout(dgb) would give, without dgb.  C % 64 == 0, 256 % (C/4) == 0, H, W % 4 == 0.
  * workspace: dsee_modulate_bwd_wino_workspace(). */
-static int wino_reduce_blocks(int N, int H, int W, int C) {
-  const long total = (long)N * (H / 4) * (W / 4) * (C / 4);
-  long b = (total + 255) / 256;
-  return (int)(b < 2048 ? b : 2048);
+// blocks per statistics group (G = 1: the whole batch; G = N: one image)
+static int wino_reduce_blocks(int N, int H, int W, int C, int G = 1) {
+  const long total = (long)(N / G) * (H / 4) * (W / 4) * (C / 4);
+  const long b = (total + 255) / 256, cap = G == 1 ? 2048 : (2048 / G > 1 ? 2048 / G : 1);
+  return (int)(b < cap ? b : cap);
 }
 
 size_t dsee_modulate_bwd_wino_workspace(int N, int H, int W, int C) {
+  return dsee_modulate_bwd_wino_workspace_sg(N, H, W, C, 1);
+}
+
+size_t dsee_modulate_bwd_wino_workspace_sg(int N, int H, int W, int C, int stat_groups) {
+  if (stat_groups < 1 || N % stat_groups) return 0;
   // fp32 form: one row [4][C] per block; pre-split form: one row [4][64] per wave (4 per block)
-  return (size_t)(wino_reduce_blocks(N, H, W, C) + 4) * 4 * (C > 256 ? C : 256) * sizeof(float);   // (+4: grid rounded up to C/64 groups)
+  return (size_t)stat_groups * (wino_reduce_blocks(N, H, W, C, stat_groups) + 4) * 4 * (C > 256 ? C : 256) *
+         sizeof(float);   // (+4: grid rounded up to C/64 groups)
 }
 
 int dsee_modulate_bwd_reduce_wino(const float* dh, const float* h, const float* x, const float* scale, const float* mean,
                                   const float* invstd, float* dM, int rows, float* sums, int N, int H, int W, int C,
                                   float slope, float* workspace, float* amax, hipStream_t st) {
+  return dsee_modulate_bwd_reduce_wino_sg(dh, h, x, scale, mean, invstd, dM, rows, sums, N, H, W, C, 1, slope, workspace,
+                                          amax, st);
+}
+
+int dsee_modulate_bwd_reduce_wino_sg(const float* dh, const float* h, const float* x, const float* scale,
+                                     const float* mean, const float* invstd, float* dM, int rows, float* sums, int N, int H,
+                                     int W, int C, int stat_groups, float slope, float* workspace, float* amax,
+                                     hipStream_t st) {
   DSEE_CHECK_ARG(dh && h && x && scale && mean && invstd && dM && sums && workspace);
   DSEE_CHECK_ARG(C % 64 == 0 && C <= 1024 && 256 % (C / 4) == 0 && rows == 2 * C && H % 4 == 0 && W % 4 == 0);
   DSEE_CHECK_ARG((long)N * H * W * C / 64 < (1L << 32));      // (32-bit item index in the kernels: dsee_common.h)
-  const int blocks = wino_reduce_blocks(N, H, W, C);
-  norm_bwd_reduce_wino_kernel<<<blocks, 256, 0, st>>>(dh, h, x, scale, mean, invstd, dM, rows, workspace, N, H, W, C,
-                                                      slope, amax);
+  DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == N);
+  const int blocks = wino_reduce_blocks(N, H, W, C, stat_groups);
+  norm_bwd_reduce_wino_kernel<<<dim3(blocks, stat_groups), 256, 0, st>>>(dh, h, x, scale, mean, invstd, dM, rows,
+                                                                         workspace, N, H, W, C, slope, amax);
   DSEE_LAUNCH_CHECK();
-  RedGeom g = make_geom(N, H * W, C, 1);
-  g.chunks = blocks;  // one partial row [4][C] per block
-  sums_finalize_kernel<<<dsee_cdiv((long)4 * C, 8), 256, 0, st>>>(workspace, sums, 4, g);
+  if (stat_groups == 1) {
+    RedGeom g = make_geom(N, H * W, C, 1);
+    g.chunks = blocks;  // one partial row [4][C] per block
+    sums_finalize_kernel<<<dsee_cdiv((long)4 * C, 8), 256, 0, st>>>(workspace, sums, 4, g);
+  } else {
+    sums_finalize_sg_kernel<<<dsee_cdiv((long)(2 * stat_groups + 2) * C, 8), 256, 0, st>>>(workspace, sums, blocks,
+                                                                                           stat_groups, C);
+  }
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }
@@ -963,17 +1022,27 @@ int dsee_modulate_bwd_apply_amax(const float* dh, const float* h, const float* x
                                  const float* invstd, const float* sums, const float* add, float* dx, int N, int HW, int C,
                                  float inv_count, float slope, float* amax_dx, int scale_f16, const uint32_t* sign_mask,
                                  hipStream_t st) {
+  return dsee_modulate_bwd_apply_amax_sg(dh, h, x, scale, mean, invstd, sums, add, dx, N, HW, C, 1, inv_count, slope, amax_dx,
+                                         scale_f16, sign_mask, st);
+}
+
+int dsee_modulate_bwd_apply_amax_sg(const float* dh, const float* h, const float* x, const float* scale, const float* mean,
+                                    const float* invstd, const float* sums, const float* add, float* dx, int N, int HW, int C,
+                                    int stat_groups, float inv_count, float slope, float* amax_dx, int scale_f16,
+                                    const uint32_t* sign_mask, hipStream_t st) {
   DSEE_CHECK_ARG(dh && (h || sign_mask) && x && scale && mean && invstd && sums && dx && amax_dx && C % 4 == 0 && inv_count > 0.f);
   DSEE_CHECK_ARG(!sign_mask || C % 32 == 0);
+  DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == N);
   const long total4 = (long)N * HW * C / 4;
   DSEE_CHECK_ARG(total4 < (1L << 32));
+  const long ge = (long)(N / stat_groups) * HW * C;
   if (scale_f16)
     norm_bwd_apply_kernel<1, true><<<grid_for(total4), 256, 0, st>>>(dh, h, x, scale, mean, invstd, sums, add, dx, total4, C,
-                                                                     (long)N * HW * C, 1, inv_count, DSEE_ACT_LRELU, slope,
+                                                                     ge, stat_groups, inv_count, DSEE_ACT_LRELU, slope,
                                                                      amax_dx, sign_mask);
   else
     norm_bwd_apply_kernel<1><<<grid_for(total4), 256, 0, st>>>(dh, h, x, scale, mean, invstd, sums, add, dx, total4, C,
-                                                               (long)N * HW * C, 1, inv_count, DSEE_ACT_LRELU, slope, amax_dx,
+                                                               ge, stat_groups, inv_count, DSEE_ACT_LRELU, slope, amax_dx,
                                                                sign_mask);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;

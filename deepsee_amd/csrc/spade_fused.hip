@@ -518,7 +518,9 @@ __global__ __launch_bounds__(512) void spade_fused_fwd_kernel(FusedArgs a) {
   float* const Gs = reinterpret_cast<float*>(smem);
   float* const Bs = reinterpret_cast<float*>(smem + 32768);
   const int tl_w = 16 * wt + fi;                          // this lane's tile within the block
-  const f32x4 mu = *reinterpret_cast<const f32x4*>(a.mean + cq), is = *reinterpret_cast<const f32x4*>(a.invstd + cq);
+  // (a block's 64 tiles lie in one image, tpi % 64 == 0: image n's statistics row)
+  const int sq = n * a.stat_ld + cq;
+  const f32x4 mu = *reinterpret_cast<const f32x4*>(a.mean + sq), is = *reinterpret_cast<const f32x4*>(a.invstd + sq);
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   const f32x4 bg = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + rg * 64 + chunk_r * 4) : z4;
   const f32x4 bb = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + rg * 64 + 32 + chunk_r * 4) : z4;
@@ -898,7 +900,9 @@ __global__ __launch_bounds__(1024) void spade_fused_fwd16_kernel(FusedArgs a) {
   float* const Bs = reinterpret_cast<float*>(smem + 32768);
   float* const Ws = is_beta ? Bs : Gs;                    // this wave's half of the exchange
   const int tl_w = 16 * wt + fi;
-  const f32x4 mu = *reinterpret_cast<const f32x4*>(a.mean + cq), is = *reinterpret_cast<const f32x4*>(a.invstd + cq);
+  // (a block's 64 tiles lie in one image, tpi % 64 == 0: image n's statistics row)
+  const int sq = n * a.stat_ld + cq;
+  const f32x4 mu = *reinterpret_cast<const f32x4*>(a.mean + sq), is = *reinterpret_cast<const f32x4*>(a.invstd + sq);
   const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
   const f32x4 bg = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + rg * 64 + chunk_r * 4) : z4;
   const f32x4 bb = a.bias ? *reinterpret_cast<const f32x4*>(a.bias + rg * 64 + 32 + chunk_r * 4) : z4;
@@ -1002,11 +1006,12 @@ extern "C" void dsee_fused_set_stamps(float* p) { g_fused_stamps = p; }
 static int spade_fused_launch(bool packed, const void* V2, const void* U2, const float* amax_cat, float v_bound,
                               const float* amax_u, const float* bias_packed, const float* x, const float* mean,
                               const float* invstd, float* out_h, float* out_scale, int N, int H, int W, int C, int rows, int K,
-                              int groups, float add_one, float slope, float* amax_h, float* amax_xhat, unsigned* sign_mask,
-                              hipStream_t st) {
+                              int groups, int stat_groups, float add_one, float slope, float* amax_h, float* amax_xhat,
+                              unsigned* sign_mask, hipStream_t st) {
   DSEE_CHECK_ARG(V2 && U2 && amax_cat && amax_u && x && mean && invstd && out_h);
   DSEE_CHECK_ARG(rows == 2 * C && C % 32 == 0 && H % 4 == 0 && W % 4 == 0 && (K == 128 || K == 160));
   DSEE_CHECK_ARG(groups == 1 || groups == N);
+  DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == N);
   const int tpi = (H / 4) * (W / 4);
   DSEE_CHECK_ARG(tpi % 64 == 0);
   const long T = (long)N * tpi;
@@ -1019,6 +1024,7 @@ static int spade_fused_launch(bool packed, const void* V2, const void* U2, const
   a.x = x;
   a.mean = mean;
   a.invstd = invstd;
+  a.stat_ld = stat_groups == 1 ? 0 : C;
   a.out = out_h;
   a.scale = out_scale;
   a.mask = sign_mask;
@@ -1102,7 +1108,7 @@ int dsee_spade_fused_fwd(const void* V2, const void* U2, const float* amax_cat, 
                          float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, float add_one,
                          float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask, hipStream_t st) {
   return spade_fused_launch(false, V2, U2, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
-                            C, rows, K, groups, add_one, slope, amax_h, amax_xhat, sign_mask, st);
+                            C, rows, K, groups, 1, add_one, slope, amax_h, amax_xhat, sign_mask, st);
 }
 
 /* 16-bit storage mode: the same kernel on PACKED ONE-TERM operands -- V1 = dsee_wino43_input_f16p(cat) [K/32][36*T][32] fp16,
@@ -1112,7 +1118,25 @@ int dsee_spade_fused_fwd_f16p(const void* V1, const void* U1, const float* amax_
                               float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, float add_one,
                               float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask, hipStream_t st) {
   return spade_fused_launch(true, V1, U1, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
-                            C, rows, K, groups, add_one, slope, amax_h, amax_xhat, sign_mask, st);
+                            C, rows, K, groups, 1, add_one, slope, amax_h, amax_xhat, sign_mask, st);
+}
+
+/* ... with `stat_groups` = 1 (BatchNorm: mean / invstd [C]) or N (InstanceNorm: [N][C], one row per image) */
+int dsee_spade_fused_fwd_sg(const void* V2, const void* U2, const float* amax_cat, float v_bound, const float* amax_u,
+                            const float* bias_packed, const float* x, const float* mean, const float* invstd, float* out_h,
+                            float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, int stat_groups,
+                            float add_one, float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask, hipStream_t st) {
+  return spade_fused_launch(false, V2, U2, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
+                            C, rows, K, groups, stat_groups, add_one, slope, amax_h, amax_xhat, sign_mask, st);
+}
+
+int dsee_spade_fused_fwd_f16p_sg(const void* V1, const void* U1, const float* amax_cat, float v_bound, const float* amax_u,
+                                 const float* bias_packed, const float* x, const float* mean, const float* invstd,
+                                 float* out_h, float* out_scale, int N, int H, int W, int C, int rows, int K, int groups,
+                                 int stat_groups, float add_one, float slope, float* amax_h, float* amax_xhat,
+                                 uint32_t* sign_mask, hipStream_t st) {
+  return spade_fused_launch(true, V1, U1, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
+                            C, rows, K, groups, stat_groups, add_one, slope, amax_h, amax_xhat, sign_mask, st);
 }
 
 }  // extern "C"

@@ -18,8 +18,9 @@ struct FusedArgs {
   const float* amax_u;
   const float* bias;         // packed [rows]
   const float* x;
-  const float* mean;
+  const float* mean;         // [C] (BatchNorm) or [N][C] (InstanceNorm: stat_ld = C)
   const float* invstd;
+  int stat_ld;               // floats between two images' statistics rows: 0 (one row for the batch) or C
   float* out;
   float* amax_h;   // optional: max |out| (64-line form) -- the operand bound of the convolution that consumes h
   float* amax_xhat;   // optional: max |xhat| -- with max |dh| the bound of the backward pass's gamma/beta gradient

@@ -449,6 +449,7 @@ int dsee_spade_fused_fwd_w4(const void* V2, const void* U2, const float* amax_ca
   a.x = x;
   a.mean = mean;
   a.invstd = invstd;
+  a.stat_ld = 0;     // (BatchNorm statistics only: InstanceNorm layers take dsee_spade_fused_fwd_sg)
   a.out = out_h;
   a.scale = out_scale;
   a.mask = sign_mask;

@@ -792,7 +792,7 @@ __global__ __launch_bounds__(256, 2) void wino43_output_modulate_kernel(
     const TM* __restrict__ M, const float* __restrict__ bias, const float* __restrict__ x,
     const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ out,
     float* __restrict__ scale, int N, int H, int W, int C, int rows, float add_one, float slope,
-    const float* __restrict__ mscale) {
+    const float* __restrict__ mscale, int stat_ld) {
   const float ms = mscale ? *mscale : 1.f;
   const int C4 = C / 4, th = H / 4, tw = W / 4;
   const long T = (long)N * th * tw, total = T * C4;
@@ -806,7 +806,9 @@ __global__ __launch_bounds__(256, 2) void wino43_output_modulate_kernel(
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     const f32x4 bg = bias ? *reinterpret_cast<const f32x4*>(bias + pg) : z4;
     const f32x4 bb = bias ? *reinterpret_cast<const f32x4*>(bias + pg + 32) : z4;
-    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c), is = *reinterpret_cast<const f32x4*>(invstd + c);
+    // (stat_ld = C: InstanceNorm statistics, one row per image)
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + n * stat_ld + c);
+    const f32x4 is = *reinterpret_cast<const f32x4*>(invstd + n * stat_ld + c);
     // gamma first: scale = gamma + bias + add_one is stored and folded with x-hat into y = x-hat * scale, then beta.  One
     // 4x4 tile of 16 float4 is live across the second transform instead of two (422 -> < 256 VGPRs: two waves per SIMD,
     // so the load phase of one wave overlaps the store phase of the other).
@@ -1684,6 +1686,15 @@ int dsee_wino43_weights_batch(const float* w_oihw, float* U, int layers, long w_
 int dsee_wino43_output_modulate(const float* M, const float* bias_packed, const float* x, const float* mean,
                                 const float* invstd, float* out_h, float* out_scale, int N, int H, int W, int C,
                                 int rows, float add_one, float slope, const float* mscale, hipStream_t st) {
+  return dsee_wino43_output_modulate_sg(M, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W, C, rows, 1, add_one, slope,
+                                        mscale, st);
+}
+
+int dsee_wino43_output_modulate_sg(const float* M, const float* bias_packed, const float* x, const float* mean,
+                                   const float* invstd, float* out_h, float* out_scale, int N, int H, int W, int C, int rows,
+                                   int stat_groups, float add_one, float slope, const float* mscale, hipStream_t st) {
+  DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == N);
+  const int stat_ld = stat_groups == 1 ? 0 : C;
   DSEE_CHECK_ARG(wino_items32(N, H, W, C));      // (32-bit item index in the kernels: dsee_common.h)
   DSEE_CHECK_ARG(M && x && mean && invstd && out_h && C % 64 == 0 && rows == 2 * C);  // out_scale may be NULL
   DSEE_CHECK_ARG(H % 4 == 0 && W % 4 == 0);
@@ -1691,10 +1702,10 @@ int dsee_wino43_output_modulate(const float* M, const float* bias_packed, const 
   const int grid = wgrid((long)N * (H / 4) * (W / 4) * (C / 4));
   if (mscale)
     wino43_output_modulate_kernel<<<grid, 256, 0, st>>>(reinterpret_cast<const _Float16*>(M), bias_packed, x, mean, invstd,
-                                                        out_h, out_scale, N, H, W, C, rows, add_one, slope, mscale);
+                                                        out_h, out_scale, N, H, W, C, rows, add_one, slope, mscale, stat_ld);
   else
     wino43_output_modulate_kernel<<<grid, 256, 0, st>>>(M, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W, C, rows,
-                                                        add_one, slope, nullptr);
+                                                        add_one, slope, nullptr, stat_ld);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }

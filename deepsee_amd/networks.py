@@ -9,6 +9,7 @@ into producers/consumers.
 Reference: deepsee_models/networks/{sr,architecture,normalization,encoder,discriminator,loss}.py.
 """
 import math
+import re
 
 import torch
 import torch.nn as nn
@@ -70,6 +71,31 @@ class BNStats(nn.Module):
         self.register_buffer("running_mean", torch.zeros(c))
         self.register_buffer("running_var", torch.ones(c))
         self.register_buffer("num_batches_tracked", torch.zeros((), dtype=torch.long))  # never incremented
+
+
+_NORM_G_RE = re.compile(r"(?:sean|spade)(\D+)(\d)x\d")
+
+
+def param_free_norm_of(norm_G):
+    """The param-free normalisation inside every SPADE / SEAN / PureSEAN layer of the generator, parsed from opt.norm_G as the
+    reference does (normalization.py:76-92, 130-143, 223-236: `spade(\\D+)(\\d)x\\d` / `sean(...)` / `latesean(...)` after
+    removing 'spectral'): "instance" (nn.InstanceNorm2d(affine=False): per image and channel, batch statistics in eval too)
+    or "batch" ('syncbatch' and 'batch': BatchNorm, sync-free per shard unless opt.sync_bn).  The type is compared exactly
+    (the reference tests substrings, so it would also take e.g. 'fooinstance'); any other type raises ValueError.  What this
+    build does not implement -- a generator without spectral norm, a SPADE kernel size other than 3 -- raises
+    NotImplementedError instead of training something else."""
+    m = _NORM_G_RE.search(norm_G.replace("spectral", ""))
+    if m is None:
+        raise ValueError("norm_G %r: expected spectral{spade,sean,latesean}<norm><k>x<k>" % norm_G)
+    kind = m.group(1)
+    out = {"instance": "instance", "syncbatch": "batch", "batch": "batch"}.get(kind)
+    if out is None:
+        raise ValueError("%s is not a recognized param-free norm type in SPADE" % kind)
+    if int(m.group(2)) != 3:
+        raise NotImplementedError("norm_G %r: only 3x3 SPADE / SEAN convolutions are implemented" % norm_G)
+    if "spectral" not in norm_G:
+        raise NotImplementedError("norm_G %r: only the spectral-norm generator is implemented" % norm_G)
+    return out
 
 
 class VecP(nn.Module):
@@ -215,10 +241,12 @@ class SpadeNorm(nn.Module):
     """normalization.py: SPADE (:71-120), SEAN_Block (:123-213), PureSEAN_Block (:216-286) followed by the
     resblock's LeakyReLU (architecture.py:92,114)."""
 
-    def __init__(self, kind, c, label_nc, style_size, max_fm_size):
+    def __init__(self, kind, c, label_nc, style_size, max_fm_size, norm="batch"):
         super().__init__()
         self.kind, self.c, self.max_fm = kind, c, max_fm_size
-        self.param_free_norm = BNStats(c)
+        # InstanceNorm keeps no running statistics: no buffers, the reference's state-dict keys (ops.norm_stats)
+        self.param_free_norm = BNStats(c) if norm == "batch" else None
+        self.norm = norm
         attach(self, "mlp_shared.0", ConvP(NHIDDEN, label_nc, 3))
         if kind in ("spade", "sean"):
             self.mlp_gamma = ConvP(c, NHIDDEN, 3)
@@ -231,13 +259,17 @@ class SpadeNorm(nn.Module):
             self.alpha_beta = nn.Parameter(torch.rand(1))
             self.alpha_gamma = nn.Parameter(torch.rand(1))
 
+    def _running(self):
+        """(running_mean, running_var) of a BatchNorm layer; (None, None) selects InstanceNorm statistics in ops."""
+        st = self.param_free_norm
+        return (st.running_mean, st.running_var) if st is not None else (None, None)
+
     def forward(self, x, labels, style, training, grad_sink=None):
         """`grad_sink` (ops.GradSink): the gradient of the other consumer of x (the resblock shortcut) is added to dx
         inside this norm's backward pass."""
         n, h, w, c = x.shape
         fm = h if self.kind == "spade" else min(h, self.max_fm)  # SPADE.forward has no fm cap
         sh = self.mlp_shared._modules["0"]
-        st = self.param_free_norm
         capped = fm != h
         if capped and (h * w) % 128 == 0 and c % 64 == 0:
             return self._forward_capped(x, labels, training, fm, grad_sink)
@@ -251,7 +283,7 @@ class SpadeNorm(nn.Module):
             w2a, _, b2 = P(0, self.mlp_gamma.weight, self.mlp_beta.weight, None, None, self.mlp_gamma.bias,
                            self.mlp_beta.bias, None, None, None, None, am)
             w2a.dsee_amax = am
-            return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, None, b2, st.running_mean, st.running_var,
+            return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, None, b2, *self._running(),
                                            labels, shift, training, 1.0, grad_sink)
         if self.kind == "sean":
             w2a, wst, b2 = P(1, self.mlp_gamma.weight, self.mlp_beta.weight, self.mlp_style_gamma.weight,
@@ -259,13 +291,13 @@ class SpadeNorm(nn.Module):
                              self.mlp_style_gamma.bias, self.mlp_style_beta.bias, self.alpha_gamma, self.alpha_beta, am)
             w2a.dsee_amax = am
             table = ops.style_table_packed(style, wst, b2.shape[0], am)
-            return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, table, b2, st.running_mean, st.running_var,
+            return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, table, b2, *self._running(),
                                            labels, shift, training, 1.0, grad_sink)
         # puresean: out = xhat * gamma_s + beta_s
         _, wst, b2 = P(2, None, None, self.mlp_style_gamma.weight, self.mlp_style_beta.weight, None, None,
                        self.mlp_style_gamma.bias, self.mlp_style_beta.bias, None, None, None)
         table = ops.style_table_packed(style, wst, b2.shape[0], am)
-        return ops.SeanNormTable.apply(x, None, None, None, table, b2, st.running_mean, st.running_var, labels, shift,
+        return ops.SeanNormTable.apply(x, None, None, None, table, b2, *self._running(), labels, shift,
                                        training, 0.0, grad_sink)
 
     def _forward_capped(self, x, labels, training, fm, grad_sink=None):
@@ -274,7 +306,7 @@ class SpadeNorm(nn.Module):
         nearest-upsampled (the style matrix is ignored; it only type-checks because nhidden == style size), so the two
         weight sets act on the same 128 channels and fold into one: gamma/beta = conv(up(actv), W_folded)."""
         n, h, w, c = x.shape
-        sh, st = self.mlp_shared._modules["0"], self.param_free_norm
+        sh = self.mlp_shared._modules["0"]
         ups = int(round(math.log2(h // fm)))
         am = ops.amax_slot()
         if self.kind == "sean":
@@ -288,7 +320,7 @@ class SpadeNorm(nn.Module):
                                             self.mlp_style_gamma.bias, self.mlp_style_beta.bias, None, None, None, None, am)
             add_one = 0.0
         w2a.dsee_amax = am
-        return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, None, b2, st.running_mean, st.running_var, labels,
+        return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, None, b2, *self._running(), labels,
                                        labels.shift_for(fm), training, add_one, grad_sink, ups)
 
     def _forward_dense(self, x, labels, style, training, fm, grad_sink=None):
@@ -329,8 +361,7 @@ class SpadeNorm(nn.Module):
             w2, b2 = ops.pack_gamma_beta(self.mlp_style_gamma.weight, self.mlp_style_beta.weight,
                                          self.mlp_style_gamma.bias, self.mlp_style_beta.bias)
             add_one = 0.0
-        st = self.param_free_norm
-        return ops.SpadeNormAct.apply(x, cat, w2, b2, st.running_mean, st.running_var, training, add_one, cat_ups,
+        return ops.SpadeNormAct.apply(x, cat, w2, b2, *self._running(), training, add_one, cat_ups,
                                       grad_sink)
 
 
@@ -342,8 +373,9 @@ class SPADEResnetBlock(nn.Module):
         self.kind, self.add_noise_cfg = kind, bool(opt.add_noise)
         self.conv_0 = SNConvP(c, c, 3, True)
         self.conv_1 = SNConvP(c, c, 3, True)
-        self.norm_0 = SpadeNorm(kind, c, opt.semantic_nc, opt.regional_style_size, opt.max_fm_size)
-        self.norm_1 = SpadeNorm(kind, c, opt.semantic_nc, opt.regional_style_size, opt.max_fm_size)
+        norm = param_free_norm_of(opt.norm_G) if hasattr(opt, "norm_G") else "batch"    # (an opt without norm_G: BatchNorm)
+        self.norm_0 = SpadeNorm(kind, c, opt.semantic_nc, opt.regional_style_size, opt.max_fm_size, norm)
+        self.norm_1 = SpadeNorm(kind, c, opt.semantic_nc, opt.regional_style_size, opt.max_fm_size, norm)
         if self.add_noise_cfg:
             self.noise_in, self.noise_skip, self.noise_middle = VecP(c), VecP(c), VecP(c)
 

@@ -1582,18 +1582,67 @@ def bn_stats(x, running_mean, running_var, training):
     return mean, invstd, cfg
 
 
+def in_stats(x):
+    """(mean, invstd) [N][C] of the param-free InstanceNorm2d(affine=False) inside SPADE/SEAN (normalization.py:84-85):
+    per image and channel, biased variance + eps, no running statistics -- batch statistics in training and eval alike, and
+    never all-reduced.  norm_0 and norm_s of a resblock normalise the same tensor: one partial pass, finalized per layer."""
+    n, h, w, c = x.shape
+    mean, invstd = new(n, c), new(n, c)
+    part = getattr(x, "dsee_in_part", None)
+    if part is None:
+        part = torch.empty(L.lib().dsee_norm_workspace(n, h * w, c, n) // 4, dtype=torch.float32, device="cuda")
+        L.call("norm_stats_partial", x, n, h * w, c, n, part)
+        if P().share_stats:
+            x.dsee_in_part = part
+    L.call("norm_stats_finalize", part, n, h * w, c, n, BN_EPS, BN_MOMENTUM, mean, invstd, None, None)
+    return mean, invstd
+
+
+def norm_stats(x, running_mean, running_var, training):
+    """(mean, invstd, synced) of a SPADE/SEAN param-free norm: BatchNorm ([C], bn_stats) for a layer with running statistics,
+    InstanceNorm ([N][C], in_stats) for one without (networks.SpadeNorm with norm_G ...instance...)."""
+    if running_mean is None:
+        mean, invstd = in_stats(x)
+        return mean, invstd, None
+    return bn_stats(x, running_mean, running_var, training)
+
+
+def stat_groups(mean):
+    """1 for BatchNorm statistics [C], N for InstanceNorm statistics [N][C] (the `stat_groups` of the _sg entry points)."""
+    return mean.shape[0] if mean.dim() == 2 else 1
+
+
+def _call_sg(name, sg, head, tail):
+    """dsee_<name>(*head, *tail) for BatchNorm statistics (sg = 1: the entry point and launches of the BatchNorm path as
+    they are), dsee_<name>_sg(*head, sg, *tail) for InstanceNorm statistics."""
+    if sg == 1:
+        L.call(name, *head, *tail)
+    else:
+        L.call(name + "_sg", *head, sg, *tail)
+
+
+def _wino_ws(n, h, w, c, sg):
+    return (L.lib().dsee_modulate_bwd_wino_workspace(n, h, w, c) if sg == 1
+            else L.lib().dsee_modulate_bwd_wino_workspace_sg(n, h, w, c, sg))
+
+
 def modulate_bwd(dh, out, x, scale, mean, invstd, rows, cfg, as_dm=False, add=None, xhat_amax=None, mask=None):
     """Backward of BN + modulate + LeakyReLU: (dx, dgb, col_sums [2][C], dM).  With SyncBN (`cfg`) the two per-channel
     sums of the BN backward are all-reduced over the ranks between the reduce and the apply pass.  `as_dm`: the
     gamma/beta gradient leaves the reduce pass as dM = A (g*xhat | g) A^T [36][T][rows] (dgb is None).  `mask`: the LeakyReLU
-    branch of `out` as bits (written by the fused forward); the passes that take it do not read `out`."""
+    branch of `out` as bits (written by the fused forward); the passes that take it do not read `out`.
+    InstanceNorm statistics (mean [N][C]): the two sums of the norm backward are per image ([2][N][C]), the bias gradients
+    col_sums stay per channel."""
     n, h, w, c = x.shape
+    sg = stat_groups(mean)
     dx = torch.empty_like(x)
-    sums = new(4, c)
+    sums = new(2 * sg + 2, c)
     dgb = dm = None
     t = n * (h // 4) * (w // 4)
     dha = carried_amax(dh)
-    pre = as_dm and P().presplit_dm and P().presplit_gb and xhat_amax is not None and dha is not None and t % 256 == 0
+    # (the pre-split reduce passes take BatchNorm statistics only: an InstanceNorm layer writes an fp32 dM in both precisions)
+    pre = (as_dm and P().presplit_dm and P().presplit_gb and xhat_amax is not None and dha is not None and t % 256 == 0
+           and sg == 1)
     s16 = scale.dtype == torch.float16       # written by dsee_spade_fused_fwd_f16p (16-bit storage mode)
     if s16 and not (pre and P().half):
         scale, s16 = scale.float(), False    # (a pass the packed kernels do not take: they read fp32)
@@ -1611,30 +1660,32 @@ def modulate_bwd(dh, out, x, scale, mean, invstd, rows, cfg, as_dm=False, add=No
                DM_BOUND, mask)
     elif as_dm:
         dm = (new(36, t, rows), amax_slot() if (P().gemm_split and (P().gemm_f16x2 or P().half)) else None)
-        ws = scratch(L.lib().dsee_modulate_bwd_wino_workspace(n, h, w, c), "norm")
-        L.call("modulate_bwd_reduce_wino", dh.contiguous(), out, x, scale, mean, invstd, dm[0], rows, sums, n, h, w, c,
-               LRELU_SLOPE, ws, dm[1])
+        ws = scratch(_wino_ws(n, h, w, c, sg), "norm")
+        _call_sg("modulate_bwd_reduce_wino", sg, (dh.contiguous(), out, x, scale, mean, invstd, dm[0], rows, sums, n, h, w, c),
+                 (LRELU_SLOPE, ws, dm[1]))
     else:
         dgb = (torch.zeros if c % 64 else torch.empty)(n, h, w, rows, dtype=torch.float32, device=x.device)
-        ws = scratch(L.lib().dsee_norm_workspace(n, h * w, c, 1), "norm")
-        L.call("modulate_bwd_reduce", dh.contiguous(), out, x, scale, mean, invstd, dgb, rows, sums, n, h * w, c,
-               LRELU_SLOPE, ws)
-    count = n * h * w
-    if cfg is not None:
+        ws = scratch(L.lib().dsee_norm_workspace(n, h * w, c, sg), "norm")
+        _call_sg("modulate_bwd_reduce", sg, (dh.contiguous(), out, x, scale, mean, invstd, dgb, rows, sums, n, h * w, c),
+                 (LRELU_SLOPE, ws))
+    count = (n // sg) * h * w
+    if cfg is not None:        # (BatchNorm only: InstanceNorm statistics are per image, never all-reduced)
         from . import parallel
         parallel.allreduce_sums(sums[0:2], cfg.world, cfg.group)
         count *= cfg.world
     da = amax_slot()             # max |dx|: dx is the output gradient of the convolution in front of this norm
     # dx += add: the gradient of the other consumer of x (the resblock shortcut)
-    L.call("modulate_bwd_apply_amax", dh.contiguous(), None if mask is not None else out, x, scale, mean, invstd, sums, add, dx,
-           n, h * w, c, 1.0 / count, LRELU_SLOPE, da, int(s16), mask)
+    _call_sg("modulate_bwd_apply_amax", sg,
+             (dh.contiguous(), None if mask is not None else out, x, scale, mean, invstd, sums, add, dx, n, h * w, c),
+             (1.0 / count, LRELU_SLOPE, da, int(s16), mask))
     tag_amax(dx, da)
-    return dx, dgb, sums[2:4], dm
+    return dx, dgb, sums[2 * sg:2 * sg + 2], dm
 
 
 class SpadeNormAct(torch.autograd.Function):
     """h = lrelu(BN(x) * (conv_gamma(cat) + add_one) + conv_beta(cat)) with gamma/beta formed inside the GEMM
-    epilogue; BN = sync-free batch statistics in training, running statistics in eval."""
+    epilogue; BN = sync-free batch statistics in training, running statistics in eval.  running_mean None: InstanceNorm
+    (per-image batch statistics, norm_stats)."""
 
     @staticmethod
     def forward(ctx, x, cat, w2, b2, running_mean, running_var, training, add_one, cat_ups, grad_sink=None):
@@ -1643,15 +1694,16 @@ class SpadeNormAct(torch.autograd.Function):
         n, h, w, c = x.shape
         rows, kin = w2.shape[0], w2.shape[1]
         assert cat.shape[3] == kin and kin % 4 == 0
-        mean, invstd, ctx.sync = bn_stats(x, running_mean, running_var, training)
+        mean, invstd, ctx.sync = norm_stats(x, running_mean, running_var, training)
         geom = L.geom_fwd(n, cat.shape[1], cat.shape[2], kin, rows, 3, 1, 1, cat_ups)
         assert geom.Ho == h and geom.Wo == w
         w2 = w2.contiguous()
         out, scale = torch.empty_like(x), torch.empty_like(x)
         wp = _pack_fwd(w2, kin, geom.korder)
         with _timed(_variant(geom, True), _flops(geom)):
-            L.call("conv2d_modulate_fwd", C.byref(geom), cat, wp, None, 0, b2.contiguous(), x, mean, invstd, out, scale,
-                   c, float(add_one), LRELU_SLOPE)
+            _call_sg("conv2d_modulate_fwd", stat_groups(mean),
+                     (C.byref(geom), cat, wp, None, 0, b2.contiguous(), x, mean, invstd, out, scale, c),
+                     (float(add_one), LRELU_SLOPE))
         ctx.geom = geom
         ctx.save_for_backward(x, cat, w2, out, scale, mean, invstd)
         return out
@@ -1744,7 +1796,8 @@ class SeanNormTable(torch.autograd.Function):
         elif has_t:
             L.call("label_onehot", labels.t, cat, n, labels.h, labels.w, shift, ld, ca)
             cat_amax = None
-        mean, invstd, ctx.sync = bn_stats(x, running_mean, running_var, training)
+        mean, invstd, ctx.sync = norm_stats(x, running_mean, running_var, training)
+        sg = stat_groups(mean)
         geom = L.geom_fwd(n, h, w, ld, rows, 3, 1, 1, 0)
         assert geom.korder == 1
         if has_a:
@@ -1785,9 +1838,11 @@ class SeanNormTable(torch.autograd.Function):
                 # keeps the backward pass on `out`)
                 smask = (torch.empty(n * h * w * (c // 32), dtype=torch.int32, device=x.device)
                          if (need_scale and P().sign_mask and (c & (c - 1)) == 0) else None)
-                L.call("spade_fused_fwd_f16p" if pk else ("spade_fused_fwd_w4" if P().fused_w4 else "spade_fused_fwd"), v2, u, ac, FUSED_V_BOUND, ua, b2.contiguous(), x, mean, invstd, out,
-                       scale if need_scale else None, n, h, w, c, rows, ld, n if has_t else 1, float(add_one), LRELU_SLOPE,
-                       hm, xm, smask)
+                # (the one-wave-per-SIMD kernel takes BatchNorm statistics only: InstanceNorm layers stay on spade_fused_fwd)
+                _call_sg("spade_fused_fwd_f16p" if pk else ("spade_fused_fwd_w4" if (P().fused_w4 and sg == 1) else
+                                                            "spade_fused_fwd"), sg,
+                         (v2, u, ac, FUSED_V_BOUND, ua, b2.contiguous(), x, mean, invstd, out, scale if need_scale else None, n,
+                          h, w, c, rows, ld, n if has_t else 1), (float(add_one), LRELU_SLOPE, hm, xm, smask))
                 tag_amax(out, hm)
                 ctx.xhat_amax = xm
                 ctx.sign_mask = smask
@@ -1821,13 +1876,16 @@ class SeanNormTable(torch.autograd.Function):
                 with _timed("spade_modulate_fused", 0.0,
                             (2.0 if split == 3 else 4.0) * 36 * (px // 16) * rows
                             + 4.0 * px * c * (3 if need_scale else 2)):
-                    L.call("wino43_output_modulate", m, b2c, x[n0:n0 + nb], mean, invstd, out[n0:n0 + nb],
-                           scale[n0:n0 + nb] if need_scale else None, nb, h, w, c, rows, float(add_one), LRELU_SLOPE, ms)
+                    # (InstanceNorm: the statistics rows of this pass's images)
+                    mc, ic = (mean, invstd) if sg == 1 else (mean[n0:n0 + nb], invstd[n0:n0 + nb])
+                    _call_sg("wino43_output_modulate", 1 if sg == 1 else nb,
+                             (m, b2c, x[n0:n0 + nb], mc, ic, out[n0:n0 + nb], scale[n0:n0 + nb] if need_scale else None, nb, h,
+                              w, c, rows), (float(add_one), LRELU_SLOPE, ms))
         else:
             wp = _pack_fwd(w2a, ca, 1) if has_a else None
             with _timed(_variant(geom, True), _flops(geom)):
-                L.call("conv2d_modulate_fwd", C.byref(geom), cat, wp, tb, ca, b2.contiguous(), x, mean, invstd, out,
-                       scale, c, float(add_one), LRELU_SLOPE)
+                _call_sg("conv2d_modulate_fwd", sg, (C.byref(geom), cat, wp, tb, ca, b2.contiguous(), x, mean, invstd, out,
+                                                      scale, c), (float(add_one), LRELU_SLOPE))
         ctx.geom, ctx.labels, ctx.shift, ctx.has_a, ctx.has_t, ctx.rows = geom, labels, shift, has_a, has_t, rows
         ctx.cat_ups = cat_ups
         vcat = keep[0] if (nb and keep) else (None, None)

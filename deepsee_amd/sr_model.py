@@ -22,7 +22,9 @@ from .plan import from_opt as plan_from_opt
 
 def block_plan(opt):
     """sr.py:27-51: head_0 SPADE ('late' in norm_G), SEAN blocks, PureSEAN tail iff
-    load_size >= 512."""
+    load_size >= 512.  Every layer's param-free norm follows norm_G (networks.param_free_norm_of: raises for a norm_G this build
+    does not run)."""
+    N.param_free_norm_of(opt.norm_G)
     nb = int(round(math.log2(opt.crop_size) - math.log2(opt.start_size)))
     cfg = opt.norm_G.replace("spectral", "")
     sk = "sean" if "sean" in cfg else "spade"

@@ -500,6 +500,49 @@ int dsee_modulate_bwd_apply_amax(const float* dh, const float* h, const float* x
                                  float inv_count, float slope, float* amax_dx, int scale_f16, const uint32_t* sign_mask,
         hipStream_t stream);
 
+/* ---- InstanceNorm SPADE / SEAN / PureSEAN (opt.norm_G = spectral{spade,sean,latesean}instance3x3: normalization.py:76-92,
+ * 130-143, 223-236 with nn.InstanceNorm2d(affine=False)).  The entry points above with an explicit `stat_groups`: 1 is the
+ * BatchNorm form (statistics [C]; results bit-identical to the entry points without the suffix), N the InstanceNorm form:
+ *   mean / invstd [N][C] = dsee_norm_stats_partial / _finalize with groups = N (no running statistics: batch statistics in
+ *     training and in eval alike);
+ *   sums [2N + 2][C] = [2][N][C] (sum d, sum d*xhat per image) then [2][C] (sum g*xhat, sum g over the whole batch: the
+ *     gamma / beta bias gradients, at sums + 2 N C);
+ *   apply: inv_count = 1 / (H*W).
+ * The reduce passes keep every block inside one image and fold the partial rows in a fixed order (deterministic, no float
+ * atomics).  BatchNorm-only: the pre-split reduce passes (dsee_modulate_bwd_reduce_wino_f16x2 / _f16p) -- an InstanceNorm
+ * layer takes dsee_modulate_bwd_reduce_wino_sg (fp32 dM) in both precisions --, dsee_spade_fused_fwd_w4 and the coarse block
+ * entry points (dsee_sean_norm_fwd, dsee_spade_resblock_*). */
+int dsee_spade_fused_fwd_sg(const void* V2, const void* U2, const float* amax_cat, float v_bound, const float* amax_u,
+                            const float* bias_packed, const float* x, const float* mean, const float* invstd, float* out_h,
+                            float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, int stat_groups,
+                            float add_one, float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask,
+                            hipStream_t stream);
+int dsee_spade_fused_fwd_f16p_sg(const void* V1, const void* U1, const float* amax_cat, float v_bound, const float* amax_u,
+                                 const float* bias_packed, const float* x, const float* mean, const float* invstd,
+                                 float* out_h, float* out_scale, int N, int H, int W, int C, int rows, int K, int groups,
+                                 int stat_groups, float add_one, float slope, float* amax_h, float* amax_xhat,
+                                 uint32_t* sign_mask, hipStream_t stream);
+int dsee_wino43_output_modulate_sg(const float* M, const float* bias_packed, const float* x, const float* mean,
+                                   const float* invstd, float* out_h, float* out_scale, int N, int H, int W, int C, int rows,
+                                   int stat_groups, float add_one, float slope, const float* mscale, hipStream_t stream);
+int dsee_conv2d_modulate_fwd_sg(const dsee_conv_geom* g, const float* in, const float* w_packed,
+                                const float* style_table, int shared_cin, const float* bias_packed, const float* x,
+                                const float* mean, const float* invstd, float* out_h, float* out_scale, int C,
+                                int stat_groups, float add_one, float slope, hipStream_t stream);
+/* sums: [2 stat_groups + 2][C]; workspace: dsee_norm_workspace(N, HW, C, stat_groups) */
+int dsee_modulate_bwd_reduce_sg(const float* dh, const float* h, const float* x, const float* scale, const float* mean,
+                                const float* invstd, float* dgb, int dgb_ld, float* sums, int N, int HW, int C,
+                                int stat_groups, float slope, float* workspace, hipStream_t stream);
+size_t dsee_modulate_bwd_wino_workspace_sg(int N, int H, int W, int C, int stat_groups);
+int dsee_modulate_bwd_reduce_wino_sg(const float* dh, const float* h, const float* x, const float* scale,
+                                     const float* mean, const float* invstd, float* dM, int rows, float* sums, int N, int H,
+                                     int W, int C, int stat_groups, float slope, float* workspace, float* amax,
+                                     hipStream_t stream);
+int dsee_modulate_bwd_apply_amax_sg(const float* dh, const float* h, const float* x, const float* scale, const float* mean,
+                                    const float* invstd, const float* sums, const float* add, float* dx, int N, int HW, int C,
+                                    int stat_groups, float inv_count, float slope, float* amax_dx, int scale_f16,
+                                    const uint32_t* sign_mask, hipStream_t stream);
+
 /* ------------------------------------------------------------------ label-map kernels (uint8 [N][H][W])
  * mlp_shared = ReLU(conv3x3(one-hot)) (normalization.py:98-101) as a 9-tap gather-sum of weight columns. */
 int dsee_onehot_conv3x3_pack(const float* w_oihw, float* table, int Co, int L, hipStream_t stream);
@@ -688,6 +731,7 @@ int dsee_comm_allgather(void* comm, const void* send, void* recv, long nbytes_pe
 int dsee_comm_destroy(void* comm);
 
 /* ---- coarse entry points: whole-block ops for a host without the Python orchestration (deepsee_amd/csrc/coarse.cpp) --------
+ * (BatchNorm param-free norms only: InstanceNorm layers, opt.norm_G = ...instance3x3, run through the _sg entry points above)
  * dsee_sean_norm_fwd = ONE SPADE / SEAN normalisation + LeakyReLU of a SPADEResnetBlock, forward (normalization.py:107-120
  * SPADE when table == NULL, :167-213 SEAN with the style half as per-image tables; architecture.py:92,114), i.e. what
  * deepsee_amd/ops.py::SeanNormTable.forward enqueues on the fused fp32 path, bit-identical to it:
