@@ -729,6 +729,88 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
   if (amax) dsee_block_atomic_absmax(amax, vmax);   // (block-uniform) max |dx|: operand bound of the consumer's A dY A^T
 }
 
+// ---- affine BatchNorm + act (norm_D / norm_E = spectral{batch,sync_batch}: nn.BatchNorm2d(affine=True),
+// normalization.py:40-44).  y = act(x * s[c] + t[c]) with s = gamma * invstd, t = beta - mean * s formed once per block in LDS.
+__global__ __launch_bounds__(256) void bn_act_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                         const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta, float* __restrict__ y,
+                                                         long total4, int C, int act, float slope,
+                                                         float* __restrict__ amax) {
+  __shared__ float ss[1024], st[1024];
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const float s = gamma[c] * invstd[c];
+    ss[c] = s;
+    st[c] = beta[c] - mean[c] * s;
+  }
+  __syncthreads();
+  float vmax = 0.f;
+  const unsigned C4 = (unsigned)C >> 2;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+    const unsigned px = (unsigned)i / C4;
+    const int c = (int)((unsigned)i - px * C4) * 4;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
+    const f32x4 s = *reinterpret_cast<const f32x4*>(ss + c);
+    const f32x4 t = *reinterpret_cast<const f32x4*>(st + c);
+    f32x4 r = v * s + t;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r[k] = dsee_act(r[k], act, slope);
+    *reinterpret_cast<f32x4*>(y + i * 4) = r;
+    vmax = fmaxf(vmax, dsee_absmax4(r));
+  }
+  if (amax) dsee_block_atomic_absmax(amax, vmax);
+}
+
+// ---- its backward, pass 2: dx = gamma * invstd * (g - (S0 + xhat * S1) / M), g = dy * act'(y), S0 = sum g,
+// S1 = sum g*xhat (norm_bwd_reduce_kernel<0> + sums_finalize_kernel, groups = 1).  Block 0 also writes dgamma = S1 and
+// dbeta = S0 (optional; the rank-local sums when `local` is given: the parameter gradients of a SyncBN layer are
+// all-reduced with the other gradients, not here).
+__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(
+    const float* __restrict__ dy, const float* __restrict__ y, const float* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ sums,
+    const float* __restrict__ local, float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
+    long total4, int C, float inv_count, int act, float slope, float* __restrict__ amax) {
+  __shared__ float sa[1024], sb[1024], sm[1024], si[1024];
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    const float is = invstd[c], k = gamma[c] * is;
+    sa[c] = k;                                  // dx = k * g - (k S0 / M) - xhat * (k S1 / M)
+    sb[c] = k * sums[c] * inv_count;
+    sm[c] = k * sums[C + c] * inv_count;
+    si[c] = is;
+    if (blockIdx.x == 0) {
+      const float* src = local ? local : sums;
+      if (dgamma) dgamma[c] = src[C + c];
+      if (dbeta) dbeta[c] = src[c];
+    }
+  }
+  __syncthreads();
+  float vmax = 0.f;
+  const unsigned C4 = (unsigned)C >> 2;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total4; i += (long)gridDim.x * blockDim.x) {
+    const long e = i * 4;
+    const unsigned px = (unsigned)i / C4;
+    const int c = (int)((unsigned)i - px * C4) * 4;
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + c);
+    const f32x4 is = *reinterpret_cast<const f32x4*>(si + c);
+    const f32x4 ka = *reinterpret_cast<const f32x4*>(sa + c);
+    const f32x4 kb = *reinterpret_cast<const f32x4*>(sb + c);
+    const f32x4 km = *reinterpret_cast<const f32x4*>(sm + c);
+    const f32x4 dv = *reinterpret_cast<const f32x4*>(dy + e);
+    const f32x4 yv = *reinterpret_cast<const f32x4*>(y + e);
+    const f32x4 xh = (*reinterpret_cast<const f32x4*>(x + e) - mu) * is;
+    f32x4 gg;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gg[k] = dv[k] * dsee_act_grad_from_out(yv[k], act, slope);
+    const f32x4 r = ka * gg - kb - xh * km;
+    *reinterpret_cast<f32x4*>(dx + e) = r;
+    vmax = fmaxf(vmax, dsee_absmax4(r));
+  }
+  if (amax) dsee_block_atomic_absmax(amax, vmax);
+}
+
+__global__ void counter_inc_kernel(long long* __restrict__ counter) {
+  if (threadIdx.x == 0) counter[0] += 1;
+}
+
 int grid_for(long total4) { return (int)min(8192L, (total4 + 255) / 256); }
 
 }  // namespace
@@ -1058,6 +1140,51 @@ int dsee_modulate_bwd(const float* dh, const float* h, const float* x, const flo
   if (rc != DSEE_OK) return rc;
   (void)hipMemcpyAsync(col_sums, sums + 2 * C, (size_t)2 * C * sizeof(float), hipMemcpyDeviceToDevice, st);
   return dsee_modulate_bwd_apply(dh, h, x, scale, mean, invstd, sums, add, dx, N, HW, C, 1.0f / (float)g.P, slope, st);
+}
+
+/* ---- affine BatchNorm + act of the discriminator and the style encoders (norm_D / norm_E = spectralbatch,
+ * spectralsync_batch; normalization.py:19-56).  Statistics: dsee_norm_stats_partial / _finalize with groups = 1 (training,
+ * running statistics updated) or dsee_norm_eval_stats (eval). */
+int dsee_bn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, float* y,
+                    int N, int HW, int C, int act, float slope, float* amax_y, hipStream_t st) {
+  DSEE_CHECK_ARG(x && mean && invstd && gamma && beta && y && C % 4 == 0 && C <= 1024);
+  const long total4 = (long)N * HW * C / 4;
+  DSEE_CHECK_ARG(total4 < (1L << 32));
+  bn_act_fwd_kernel<<<grid_for(total4), 256, 0, st>>>(x, mean, invstd, gamma, beta, y, total4, C, act, slope, amax_y);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_bn_act_bwd_reduce(const float* dy, const float* y, const float* x, const float* mean, const float* invstd, int N,
+                           int HW, int C, int act, float slope, float* sums, float* workspace, hipStream_t st) {
+  DSEE_CHECK_ARG(dy && y && x && mean && invstd && sums && workspace && C % 4 == 0 && C <= 1024);
+  RedGeom g = make_geom(N, HW, C, 1);
+  norm_bwd_reduce_kernel<0><<<dim3(g.chunks, 1), 256, 0, st>>>(dy, y, x, nullptr, mean, invstd, nullptr, 0, workspace, g,
+                                                               act, slope);
+  DSEE_LAUNCH_CHECK();
+  sums_finalize_kernel<<<dsee_cdiv((long)2 * C, 8), 256, 0, st>>>(workspace, sums, 2, g);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_bn_act_bwd_apply(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
+                          const float* gamma, const float* sums, const float* local_sums, float inv_count, float* dx,
+                          float* dgamma, float* dbeta, int N, int HW, int C, int act, float slope, float* amax_dx,
+                          hipStream_t st) {
+  DSEE_CHECK_ARG(dy && y && x && mean && invstd && gamma && sums && dx && C % 4 == 0 && C <= 1024);
+  const long total4 = (long)N * HW * C / 4;
+  DSEE_CHECK_ARG(total4 < (1L << 32));
+  bn_act_bwd_apply_kernel<<<grid_for(total4), 256, 0, st>>>(dy, y, x, mean, invstd, gamma, sums, local_sums, dx, dgamma,
+                                                            dbeta, total4, C, inv_count, act, slope, amax_dx);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_counter_inc(int64_t* counter, hipStream_t st) {
+  DSEE_CHECK_ARG(counter);
+  counter_inc_kernel<<<1, 64, 0, st>>>(reinterpret_cast<long long*>(counter));
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
 }
 
 }  // extern "C"

@@ -98,6 +98,71 @@ def param_free_norm_of(norm_G):
     return out
 
 
+def nonspade_norm_of(norm_type):
+    """The norm of the discriminator's and the style encoders' conv layers, parsed from opt.norm_D / opt.norm_E as the
+    reference's get_nonspade_norm_layer does (normalization.py:19-56): "instance" (InstanceNorm2d(affine=False)), "batch"
+    (nn.BatchNorm2d(affine=True)), "sync_batch" (SynchronizedBatchNorm2d(affine=True)) or "none" (the spectral-norm conv
+    alone, its bias kept).  The subtype after 'spectral' is compared exactly ('syncbatch', valid in norm_G, is not valid
+    here); any other value raises ValueError (a value without 'spectral' crashes the reference with UnboundLocalError)."""
+    if not norm_type.startswith("spectral"):
+        raise ValueError("norm type %r: expected spectral{instance,batch,sync_batch,none}" % norm_type)
+    sub = norm_type[len("spectral"):]
+    if sub in ("none", ""):
+        return "none"
+    if sub in ("instance", "batch", "sync_batch"):
+        return sub
+    raise ValueError("normalization layer %s is not recognized" % sub)
+
+
+class BatchNormP(nn.Module):
+    """Parameters and buffers of nn.BatchNorm2d(affine=True) / SynchronizedBatchNorm2d (the same state-dict entries)."""
+
+    def __init__(self, c):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(c))
+        self.bias = nn.Parameter(torch.zeros(c))
+        self.register_buffer("running_mean", torch.zeros(c))
+        self.register_buffer("running_var", torch.ones(c))
+        self.register_buffer("num_batches_tracked", torch.zeros((), dtype=torch.long))
+
+
+class NormConv:
+    """One `norm_layer(nn.Conv2d(...))` of get_nonspade_norm_layer (normalization.py:19-56) in the state-dict layout of its
+    norm.  `path` is the conv's key path under a normed layout ('model1.0.0', 'initial.0.0'): Sequential(SN conv, norm) there,
+    so the norm's entries (batch / sync_batch) sit at '<parent>.1'; with 'none' the SN conv (bias kept) replaces the
+    Sequential, one level up ('model1.0')."""
+
+    def __init__(self, root, path, cout, cin, k, norm):
+        self.norm = norm
+        parent = path.rsplit(".", 1)[0]
+        self.conv_path = parent if norm == "none" else path
+        self.bn_path = parent + ".1" if norm in ("batch", "sync_batch") else None
+        attach(root, self.conv_path, SNConvP(cout, cin, k, norm == "none"))
+        if self.bn_path is not None:
+            attach(root, self.bn_path, BatchNormP(cout))
+
+    @staticmethod
+    def _get(root, dotted):
+        m = root
+        for p in dotted.split("."):
+            m = m._modules[p]
+        return m
+
+    def conv(self, root):
+        return self._get(root, self.conv_path)
+
+    def apply(self, root, x, w, act, training, **conv_kw):
+        """act(norm(conv(x, w))): w is the conv's spectral-normalised weight of this forward."""
+        if self.norm == "none":
+            return ops.conv2d(x, w, self.conv(root).bias, act=act, **conv_kw)
+        x = ops.conv2d(x, w, None, **conv_kw)
+        if self.norm == "instance":
+            return ops.InstNormAct.apply(x, act)
+        bn = self._get(root, self.bn_path)
+        return ops.BatchNormAct.apply(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                      bn.num_batches_tracked if self.norm == "batch" else None, training, act)
+
+
 class VecP(nn.Module):
     def __init__(self, n):
         super().__init__()
@@ -438,25 +503,20 @@ class DeepSEESR(nn.Module):
 
 # ------------------------------------------------------------------------------------ style encoders
 class EncBranch(nn.Module):
-    """conv(SN, no bias) + InstanceNorm + LeakyReLU stacks of encoder.py:83-99 (full) / :142-158 (mini)."""
+    """conv(SN) + norm (opt.norm_E: InstanceNorm by default) + LeakyReLU stacks of encoder.py:83-99 (full) / :142-158 (mini)."""
 
-    def __init__(self, names, strides, ups, nf, cin):
+    def __init__(self, names, strides, ups, nf, cin, norm="instance"):
         super().__init__()
         chans = [(nf, cin), (2 * nf, nf), (4 * nf, 2 * nf), (8 * nf, 4 * nf)]
         self.names, self.strides, self.ups = names, strides, ups
-        for nm, (co, ci) in zip(names, chans):
-            attach(self, nm, SNConvP(co, ci, 3, False))
+        self.norm_layers = [NormConv(self, nm, co, ci, 3, norm) for nm, (co, ci) in zip(names, chans)]
 
-    def layer(self, nm):
-        m = self
-        for p in nm.split("."):
-            m = m._modules[p]
-        return m
+    def convs(self):
+        return [nl.conv(self) for nl in self.norm_layers]
 
     def forward_main(self, x, training):
-        for nm, s, u in zip(self.names, self.strides, self.ups):
-            x = ops.conv2d(x, self.layer(nm).weight(training), None, stride=s, pad=1, ups=u)
-            x = ops.InstNormAct.apply(x, L.ACT_LRELU)
+        for nl, s, u in zip(self.norm_layers, self.strides, self.ups):
+            x = nl.apply(self, x, nl.conv(self).weight(training), L.ACT_LRELU, training, stride=s, pad=1, ups=u)
         return x
 
 
@@ -476,25 +536,19 @@ class StyleEncoder(nn.Module):
         self.dist = opt.noisy_style_dist
         if self.scale > 0:
             self.noise_weights = nn.Parameter(torch.zeros(opt.label_nc))
-        attach(self, "final.0.0", SNConvP(s, 8 * nf, 3, False))
+        self.norm = norm = nonspade_norm_of(getattr(opt, "norm_E", "spectralinstance"))
+        self.final_layer = NormConv(self, "final.0.0", s, 8 * nf, 3, norm)
         if self.combined:
-            self.encoder_full = EncBranch(FULL_NAMES, [1, 2, 2, 1], [0, 0, 0, 1], nf, 3)
-            attach(self.encoder_full, "final.0.0", SNConvP(s, 8 * nf, 3, False))  # constructed, unused
-            self.encoder_mini = EncBranch(MINI_NAMES, [1, 1, 1, 1], [0, 0, 0, 1], nf, 3)
-            attach(self.encoder_mini, "final.0.0", SNConvP(s, 8 * nf, 3, False))  # constructed, unused
+            self.encoder_full = EncBranch(FULL_NAMES, [1, 2, 2, 1], [0, 0, 0, 1], nf, 3, norm)
+            NormConv(self.encoder_full, "final.0.0", s, 8 * nf, 3, norm)  # constructed, unused
+            self.encoder_mini = EncBranch(MINI_NAMES, [1, 1, 1, 1], [0, 0, 0, 1], nf, 3, norm)
+            NormConv(self.encoder_mini, "final.0.0", s, 8 * nf, 3, norm)  # constructed, unused
         elif opt.netE == "fullstyle":
             # FullStyleEncoder keeps its layers at the root of the state dict
             chans = [(nf, 3), (2 * nf, nf), (4 * nf, 2 * nf), (8 * nf, 4 * nf)]
-            for nm, (co, ci) in zip(FULL_NAMES, chans):
-                attach(self, nm, SNConvP(co, ci, 3, False))
+            self.norm_layers = [NormConv(self, nm, co, ci, 3, norm) for nm, (co, ci) in zip(FULL_NAMES, chans)]
         else:
             raise NotImplementedError("netE=%s (ministyle crashes in the reference too)" % opt.netE)
-
-    def _root_layer(self, nm):
-        m = self
-        for p in nm.split("."):
-            m = m._modules[p]
-        return m
 
     def forward(self, x, labels, mode, no_noise, noise, training):
         # the spectral-normalised layers THIS forward uses (the other branch's u / v must not advance: the reference's
@@ -502,20 +556,17 @@ class StyleEncoder(nn.Module):
         if mode not in self._sn:
             if self.combined:
                 br = self.encoder_full if mode == "full" else self.encoder_mini
-                layers = [br.layer(nm) for nm in br.names]
+                layers = br.convs()
             else:
-                layers = [self._root_layer(nm) for nm in FULL_NAMES]
-            self._sn[mode] = ops.SNGroup(layers + [self._root_layer("final.0.0")])
+                layers = [nl.conv(self) for nl in self.norm_layers]
+            self._sn[mode] = ops.SNGroup(layers + [self.final_layer.conv(self)])
         self._sn[mode].run(training)
         if self.combined:
             x = (self.encoder_full if mode == "full" else self.encoder_mini).forward_main(x, training)
         else:
-            for nm, s, u in zip(FULL_NAMES, [1, 2, 2, 1], [0, 0, 0, 1]):
-                x = ops.conv2d(x, self._root_layer(nm).weight(training), None, stride=s, pad=1, ups=u)
-                x = ops.InstNormAct.apply(x, L.ACT_LRELU)
-        fin = self._root_layer("final.0.0")
-        x = ops.conv2d(x, fin.weight(training), None)
-        x = ops.InstNormAct.apply(x, L.ACT_TANH)
+            for nl, s, u in zip(self.norm_layers, [1, 2, 2, 1], [0, 0, 0, 1]):
+                x = nl.apply(self, x, nl.conv(self).weight(training), L.ACT_LRELU, training, stride=s, pad=1, ups=u)
+        x = self.final_layer.apply(self, x, self.final_layer.conv(self).weight(training), L.ACT_TANH, training)
         sm = ops.StylePool.apply(x, labels, labels.shift_for(x.shape[1]))
         if self.scale > 0 and not no_noise:
             # encoder.py:51-70 on the [N,19,S] style matrix (KB-sized parameter-space glue)
@@ -539,11 +590,23 @@ class NLayerD(nn.Module):
         nf = opt.ndf
         cin = opt.label_nc + opt.output_nc + (1 if opt.contain_dontcare_label else 0)
         self.nl = opt.n_layers_D
+        self.norm = nonspade_norm_of(getattr(opt, "norm_D", "spectralinstance"))
         attach(self, "model0.0", ConvP(nf, cin, 4))
+        self.norm_layers = []
         for n in range(1, self.nl):
             prev, nf = nf, min(nf * 2, 512)
-            attach(self, "model%d.0.0" % n, SNConvP(nf, prev, 4, False))
+            self.norm_layers.append(NormConv(self, "model%d.0.0" % n, nf, prev, 4, self.norm))
         attach(self, "model%d.0" % self.nl, ConvP(1, nf, 4))
+
+    def convs(self):
+        """The spectral-normalised convolutions model1 .. model{n_layers_D - 1}."""
+        return [nl.conv(self) for nl in self.norm_layers]
+
+    @property
+    def per_sample(self):
+        """True when every layer normalises each sample on its own (InstanceNorm or no norm): D's output for one image
+        does not depend on the other images of the batch."""
+        return self.norm in ("instance", "none")
 
     def forward(self, x, training, x_detached=None):
         """`x_detached` (round 6): a second batch segment that needs no gradient -- the real images of the GENERATOR step, whose
@@ -552,7 +615,7 @@ class NLayerD(nn.Module):
         B-8), so running it as its own no-grad pass on the SAME weights of this forward (one spectral-norm power iteration) gives
         the same numbers and spares the backward pass the data gradients of a batch half whose upstream gradient is zero."""
         m0 = self.model0._modules["0"]
-        mids = [getattr(self, "model%d" % n)._modules["0"]._modules["0"].weight(training) for n in range(1, self.nl)]
+        mids = [c.weight(training) for c in self.convs()]
         ml = getattr(self, "model%d" % self.nl)._modules["0"]
 
         def run(x):
@@ -560,13 +623,14 @@ class NLayerD(nn.Module):
             x = ops.conv2d(x, m0.weight, m0.bias, stride=2, pad=2, act=L.ACT_LRELU)
             outs.append(x)
             for n in range(1, self.nl):
-                x = ops.conv2d(x, mids[n - 1], None, stride=1 if n == self.nl - 1 else 2, pad=2)
-                x = ops.InstNormAct.apply(x, L.ACT_LRELU)
+                x = self.norm_layers[n - 1].apply(self, x, mids[n - 1], L.ACT_LRELU, training,
+                                                  stride=1 if n == self.nl - 1 else 2, pad=2)
                 outs.append(x)
             outs.append(ops.conv2d(x, ml.weight, ml.bias, stride=1, pad=2))
             return outs
         if x_detached is None:
             return run(x)
+        assert self.per_sample, "norm_D=%s has batch statistics: D must run once over cat([fake; real])" % self.norm
         with torch.no_grad():
             det = run(x_detached)
         return run(x), det
@@ -582,12 +646,14 @@ class MultiscaleDiscriminator(nn.Module):
         for i in range(opt.num_D):
             self.add_module("discriminator_%d" % i, NLayerD(opt))
 
+    @property
+    def per_sample(self):
+        return all(getattr(self, "discriminator_%d" % i).per_sample for i in range(self.num_d))
+
     def forward(self, x, training, x_detached=None):
         """Returns the per-scale feature lists; with `x_detached` a pair (features of x, features of x_detached): see NLayerD."""
         if self._sn is None:
-            self._sn = ops.SNGroup([getattr(getattr(self, "discriminator_%d" % i), "model%d" % n)._modules["0"]._modules["0"]
-                                    for i in range(self.num_d)
-                                    for n in range(1, getattr(self, "discriminator_%d" % i).nl)])
+            self._sn = ops.SNGroup([c for i in range(self.num_d) for c in getattr(self, "discriminator_%d" % i).convs()])
         self._sn.run(training)
         # the scales are independent given x (and its pooled copies): one branch per scale (ops.branches)
         xs, ds = [x], [x_detached]

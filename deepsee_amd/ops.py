@@ -1280,6 +1280,54 @@ class InstNormAct(torch.autograd.Function):
         return dx, None
 
 
+class BatchNormAct(torch.autograd.Function):
+    """act(BatchNorm2d(affine=True)(x)) of the discriminator and the style encoders (opt.norm_D / opt.norm_E = spectralbatch,
+    spectralsync_batch; normalization.py:19-56): batch statistics and a running-statistics update in training (bn_stats: sync-
+    free per shard, or merged over the ranks under opt.sync_bn), the running statistics in eval.  `counter`: the layer's
+    num_batches_tracked, incremented on the device in every training forward (nn.BatchNorm2d; None for SynchronizedBatchNorm2d,
+    whose single-device branch goes through F.batch_norm and leaves it at 0)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, counter, training, act):
+        n, h, w, c = x.shape
+        mean, invstd, cfg = bn_stats(x, running_mean, running_var, training)
+        if training and counter is not None:
+            L.call("counter_inc", counter)
+        y = torch.empty_like(x)
+        ao = amax_slot() if (_direct_split_on() and P().conv_amax_out) else None    # (max |y| for the direct layer that reads y)
+        L.call("bn_act_fwd", x, mean, invstd, gamma, beta, y, n, h * w, c, act, LRELU_SLOPE, ao)
+        if ao is not None:
+            tag_amax(y, ao)
+        ctx.act, ctx.emit_amax, ctx.cfg, ctx.training = act, ao is not None, cfg, training
+        ctx.save_for_backward(x, y, mean, invstd, gamma)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        assert ctx.training, "BatchNormAct: backward of an eval-mode forward"
+        x, y, mean, invstd, gamma = ctx.saved_tensors
+        n, h, w, c = x.shape
+        dy = dy.contiguous()
+        sums = new(2, c)
+        ws = scratch(L.lib().dsee_norm_workspace(n, h * w, c, 1), "norm")
+        L.call("bn_act_bwd_reduce", dy, y, x, mean, invstd, n, h * w, c, ctx.act, LRELU_SLOPE, sums, ws)
+        count, local, cfg = n * h * w, None, ctx.cfg
+        if cfg is not None:        # SyncBN: the two sums over the global batch; the parameter gradients stay rank-local
+            from . import parallel
+            local = sums.clone()
+            parallel.allreduce_sums(sums, cfg.world, cfg.group)
+            count *= cfg.world
+        dgamma = new(c) if ctx.needs_input_grad[1] else None
+        dbeta = new(c) if ctx.needs_input_grad[2] else None
+        dx = torch.empty_like(x)
+        ao = amax_slot() if ctx.emit_amax else None    # (max |dx|: dx is a direct layer's output gradient)
+        L.call("bn_act_bwd_apply", dy, y, x, mean, invstd, gamma, sums, local, 1.0 / count, dx, dgamma, dbeta, n, h * w, c,
+               ctx.act, LRELU_SLOPE, ao)
+        if ao is not None:
+            tag_amax(dx, ao)
+        return dx, dgamma, dbeta, None, None, None, None, None
+
+
 class Act(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, act):

@@ -40,10 +40,13 @@ def block_plan(opt):
 def init_weights(net, init_type, gain, gen):
     """base_network.py:28-59 semantics on our parameter holders: xavier_normal(gain) (or kaiming / normal) on
     every conv weight incl. spectral-norm weight_orig and the unused Conv1d; biases 0; noise weights 0;
-    alpha ~ U(0,1); SN u/v ~ normalised N(0,1)."""
+    alpha ~ U(0,1); SN u/v ~ normalised N(0,1); BatchNorm2d(affine=True) of norm_D / norm_E: weight ~ N(1, gain), bias 0."""
+    bn_weights = {m + ".weight" for m, mod in net.named_modules() if isinstance(mod, N.BatchNormP)}
     for name, p in list(net.named_parameters()) + list(net.named_buffers()):
         leaf = name.split(".")[-1]
-        if leaf in ("running_mean", "num_batches_tracked"):
+        if name in bn_weights:
+            p.data.copy_(1.0 + torch.randn(p.shape, generator=gen) * gain)
+        elif leaf in ("running_mean", "num_batches_tracked"):
             p.data.zero_()
         elif leaf == "running_var":
             p.data.fill_(1.0)
@@ -340,9 +343,24 @@ class SRModel(nn.Module):
         need data gradients (their .grad is zeroed before use), so they enter detached."""
         if train_d:
             return self.netD(ops.DInput.apply(labels, fake, real), self.training)
-        # generator step (round 6): the real half enters the losses detached (sr_model.py:547-564) -- it runs as a no-grad pass of
-        # its own on the same weights (networks.NLayerD.forward), and the data gradients of the backward pass cover the generated
-        # half only.  Returns (features of the generated images, features of the real images).
+        if not self.netD.per_sample:
+            # norm_D with batch statistics (spectralbatch / spectralsync_batch): the statistics span cat([fake; real])
+            # (sr_model.py:659-663), so the real half's activations reach the generated half's gradient through them -- one
+            # pass with both halves in the graph; the real half's features enter the losses detached
+            req = [p.requires_grad for p in self.netD.parameters()]
+            for p in self.netD.parameters():
+                p.requires_grad_(False)
+            try:
+                out = self.netD(ops.DInput.apply(labels, fake, real), self.training)
+            finally:
+                for p, r in zip(self.netD.parameters(), req):
+                    p.requires_grad_(r)
+            n = fake.shape[0]
+            return out, [[t[n:].detach() for t in o] for o in out]
+        # generator step (round 6), D normalising each sample on its own (InstanceNorm or no norm; NLayerD.forward asserts
+        # it): the real half enters the losses detached (sr_model.py:547-564) -- it runs as a no-grad pass of its own on the
+        # same weights (networks.NLayerD.forward), and the data gradients of the backward pass cover the generated half only.
+        # Returns (features of the generated images, features of the real images).
         x = ops.DInput.apply(labels, fake)
         with torch.no_grad():
             xr = ops.DInput.apply(labels, real)

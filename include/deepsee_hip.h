@@ -458,6 +458,26 @@ int dsee_norm_act_fwd_amax(const float* x, const float* mean, const float* invst
 int dsee_norm_act_bwd_amax(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
                            float* dx, int N, int HW, int C, int groups, int act, float slope, float* workspace,
                            float* amax_dx, hipStream_t stream);
+/* ---- affine BatchNorm + act of the discriminator and the style encoders (opt.norm_D / opt.norm_E = spectralbatch or
+ * spectralsync_batch: nn.BatchNorm2d(affine=True) / SynchronizedBatchNorm2d behind a spectral-norm conv, normalization.py:19-56;
+ * LeakyReLU 0.2 in discriminator.py:88-93 and encoder.py:83-99, tanh in encoder.py:24-27).  mean / invstd [C] come from
+ * dsee_norm_stats_partial / _finalize with groups = 1 (training; running statistics updated) or dsee_norm_eval_stats.
+ *   fwd:    y = act(x * s + t), s = gamma * invstd, t = beta - mean * s; amax_y (optional, zeroed by the caller): max |y|
+ *   reduce: sums[2][C] = (sum g, sum g*xhat) over THIS rank's pixels, g = dy * act'(y); per-block partial rows in
+ *           `workspace` (dsee_norm_workspace(N, HW, C, 1) bytes) folded in a fixed order (bit-reproducible)
+ *   apply:  dx = gamma * invstd * (g - (sum g + xhat * sum g*xhat) * inv_count); dgamma = sum g*xhat, dbeta = sum g (both
+ *           optional) taken from local_sums when given (SyncBN: `sums` all-reduced between the passes, the parameter
+ *           gradients stay rank-local), else from sums; amax_dx (optional): max |dx|
+ * dsee_counter_inc: num_batches_tracked += 1 on the device (nn.BatchNorm2d training forward). */
+int dsee_bn_act_fwd(const float* x, const float* mean, const float* invstd, const float* gamma, const float* beta, float* y,
+                    int N, int HW, int C, int act, float slope, float* amax_y, hipStream_t stream);
+int dsee_bn_act_bwd_reduce(const float* dy, const float* y, const float* x, const float* mean, const float* invstd, int N,
+                           int HW, int C, int act, float slope, float* sums, float* workspace, hipStream_t stream);
+int dsee_bn_act_bwd_apply(const float* dy, const float* y, const float* x, const float* mean, const float* invstd,
+                          const float* gamma, const float* sums, const float* local_sums, float inv_count, float* dx,
+                          float* dgamma, float* dbeta, int N, int HW, int C, int act, float slope, float* amax_dx,
+                          hipStream_t stream);
+int dsee_counter_inc(int64_t* counter, hipStream_t stream);
 /* backward of dsee_conv2d_modulate_fwd w.r.t. x and (gamma,beta): see SURVEY.md Appendix E.
  * dgb [M][dgb_ld] is written in the packed gamma/beta column order and is the `dout` for the wgrad/dgrad of the
  * gamma/beta convolution; col_sums [2][C] = (sum g*xhat, sum g) are its bias gradients; dx gets `add` added. */
