@@ -2179,6 +2179,9 @@ class DInput(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------ losses
 MODE_L1, MODE_NEG, MODE_HINGE_REAL, MODE_HINGE_FAKE = 0, 1, 2, 3
+# the other gan_mode element losses (real label 1, fake label 0; W real is MODE_NEG): x, (x-1)^2, x^2, softplus(-x),
+# softplus(x) -- the last two are binary cross-entropy on logits
+MODE_W_FAKE, MODE_LS_REAL, MODE_LS_FAKE, MODE_BCE_REAL, MODE_BCE_FAKE = 4, 5, 6, 7, 8
 
 
 class MeanLoss(torch.autograd.Function):

@@ -73,6 +73,19 @@ def init_weights(net, init_type, gain, gen):
             p.data.copy_(torch.randn(p.shape, generator=gen) * std)
 
 
+def gan_loss_modes(gan_mode):
+    """opt.gan_mode -> the ops.mean_loss modes (generator, D real, D fake) of GANLoss (loss.py:31-40,60-85): real label 1,
+    fake label 0, each the mean over the last output of a discriminator scale.  The mode is compared exactly; any value
+    other than 'ls', 'original', 'w' or 'hinge' raises the reference's ValueError."""
+    modes = {"hinge": (ops.MODE_NEG, ops.MODE_HINGE_REAL, ops.MODE_HINGE_FAKE),
+             "w": (ops.MODE_NEG, ops.MODE_NEG, ops.MODE_W_FAKE),
+             "ls": (ops.MODE_LS_REAL, ops.MODE_LS_REAL, ops.MODE_LS_FAKE),
+             "original": (ops.MODE_BCE_REAL, ops.MODE_BCE_REAL, ops.MODE_BCE_FAKE)}
+    if not isinstance(gan_mode, str) or gan_mode not in modes:
+        raise ValueError("Unexpected gan_mode {}".format(gan_mode))
+    return modes[gan_mode]
+
+
 def _sum_terms(terms):
     """Sum of the [1]-shaped loss terms in two launches (cat + reduce) instead of one ATen add per term."""
     if not terms:        # a discriminator without intermediate features (the reference starts its sums from 0, sr_model.py:535)
@@ -96,7 +109,9 @@ class SRModel(nn.Module):
         self.netSR = N.DeepSEESR(opt, block_plan(opt))
         init_weights(self.netSR, opt.init_type, opt.init_variance, gen)
         self.netD = None
+        self.gan_modes = None
         if opt.isTrain:
+            self.gan_modes = gan_loss_modes(opt.gan_mode)     # sr_model.py:34-36: the GAN loss exists only for training
             self.netD = N.MultiscaleDiscriminator(opt)
             init_weights(self.netD, opt.init_type, opt.init_variance, gen)
         self.netE = None
@@ -310,8 +325,9 @@ class SRModel(nn.Module):
         n = fake.shape[0]
         pred, pred_real = pred      # (the generated half with its graph, the real half without: discriminate(train_d=False))
         gan = 0
+        g_mode = self.gan_modes[0]
         for p in pred:
-            gan = gan + ops.mean_loss(p[-1], None, ops.MODE_NEG, 1.0 / len(pred), valid_c=1, lo=0, hi=n)
+            gan = gan + ops.mean_loss(p[-1], None, g_mode, 1.0 / len(pred), valid_c=1, lo=0, hi=n)
         losses["GAN"] = gan
         if not opt.no_ganFeat_loss:
             terms = []
@@ -332,9 +348,10 @@ class SRModel(nn.Module):
         n = fake.shape[0]
         losses = OrderedDict()
         df = dr = 0
+        _, real_mode, fake_mode = self.gan_modes
         for p in pred:
-            df = df + ops.mean_loss(p[-1], None, ops.MODE_HINGE_FAKE, 1.0 / len(pred), valid_c=1, lo=0, hi=n)
-            dr = dr + ops.mean_loss(p[-1], None, ops.MODE_HINGE_REAL, 1.0 / len(pred), valid_c=1, lo=n, hi=2 * n)
+            df = df + ops.mean_loss(p[-1], None, fake_mode, 1.0 / len(pred), valid_c=1, lo=0, hi=n)
+            dr = dr + ops.mean_loss(p[-1], None, real_mode, 1.0 / len(pred), valid_c=1, lo=n, hi=2 * n)
         losses["D_Fake"], losses["D_Real"] = df, dr
         return losses
 

@@ -649,8 +649,11 @@ int dsee_rng_fill(float* out, long n, uint64_t seed, uint64_t offset, int normal
  * training step fresh NoiseInjection draws (normalization.py:299-304 draws a new tensor per forward). */
 int dsee_rng_set_epoch(const uint64_t* epoch_dev);
 
-/* ------------------------------------------------------------------ losses (loss.py:68-79,114-119; sr_model.py:529-539)
- * mode 0: L1(a,b)  1: -x (hinge, generator)  2: -min(x-1,0) (D, real)  3: -min(-x-1,0) (D, fake).
+/* ------------------------------------------------------------------ losses (loss.py:60-85,114-119; sr_model.py:529-539)
+ * mode 0: L1(a,b)  1: -x (hinge and W generator, W real)  2: -min(x-1,0) (hinge D, real)  3: -min(-x-1,0) (hinge D, fake)
+ *      4: x (W fake)  5: (x-1)^2 (LS real)  6: x^2 (LS fake)
+ *      7: softplus(-x) (BCE-with-logits real)  8: softplus(x) (BCE-with-logits fake); both evaluated as
+ *         max(x,0) - x*t + log1p(exp(-|x|)), gradient sigmoid(x) - t from an overflow-free sigmoid.
  * *loss_out += weight*mean; grad = weight * d mean / d a. */
 size_t dsee_loss_workspace(void);
 int dsee_loss_fwd_bwd(int mode, const float* a, const float* b, float* grad, long rows, int ld, int valid_c,
