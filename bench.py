@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the DeepSEE G+D training step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -15,7 +15,12 @@ other BASELINE configurations (guided_8x_256 = configs[3], independent_32x_512 =
 every loss term as DIR/loss_<term>.npy, float32 (see dump_outputs).  Weights, batch and noise are seeded, so two builds run with
 the same arguments can be compared file for file.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the line: the
+headline (metric, value, unit, ms_per_step, ...), the losses of the last step, `arithmetic`, `model_flops`, `peak_hbm_gb`,
+`host_enqueue_ms_per_step` and `hip_graphs`, all from the warm-up and timed steps themselves.
+  host_enqueue_ms_per_step — wall time the Python thread spends inside step() (launch enqueue; no device sync inside).
+
+`--full` adds what takes runs of its own, after the timed region (the headline figure is the same either way):
   roofline     — the dominant kernel (by summed time in a step), measured live with HIP events on the launch
                  stream in one extra instrumented step after the timed region.  Both of its rooflines are computed:
                  matrix cores (algorithmic fp32 FLOPs = 2*M*N*K of every launch / summed duration, against the peak of
@@ -29,11 +34,13 @@ Extra objects on the line:
                  path (the resource that bounds it) against the 34.5 TB/s the guide measured for L2.
   norm_forward — the WHOLE normalisation forward at the top resolution (statistics, embedding, transforms, fused kernel)
                  on SURVEY 8(d)'s algorithmic bytes (3.49 GB at N = 8, 256^2) against 8 TB/s.
-  host_enqueue_ms_per_step — wall time the Python thread spends inside step() (launch enqueue; no device sync inside).
+  launches_per_step — dsee_* C-ABI calls of the instrumented step.
   f32_mfma_only / bf16x3_exact — the same step with every GEMM kept on v_mfma_f32_32x32x2_f32 / on the exact 3-term
                  bf16 split (6 MFMA products), 3 steps each, rank 0 / N=1.
   cpu_baseline — the oracle (CPU restatement of the reference path, oracle/deepsee_oracle.py) timed on this box's
                  host cores: one G+D iteration at bs=1 of the same workload (rank 0, N=1 only).
+  dp           — N > 1: ranks seen, per-rank rates, the all-reduce alone, compute-only and rank-0-alone steps (dp_report).
+`--no-f32-run`, `--no-cpu-baseline` and `--cpu-baseline-*` shape a --full run.
 """
 import argparse
 import json
@@ -358,6 +365,9 @@ def main():
                     help="KernelPlan fields of the model (deepsee_amd/plan.py), e.g. --plan fused_norm=False (A/B runs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the generated image and the losses of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure roofline, launches_per_step, f32_mfma_only / bf16x3_exact, "
+                         "cpu_baseline and (N > 1) dp; off: only what the headline figure needs")
     args = ap.parse_args()
     if args.steps < 1:
         raise SystemExit("bench.py: --steps must be at least 1")
@@ -431,31 +441,33 @@ def main():
         outs.update(("loss_" + k, v.detach().float().cpu().numpy()) for k, v in tm.get_latest_losses().items())
         dump_outputs(args.dump_outputs, outs)
 
-    # ---- one extra instrumented step: per-launch HIP events around every MFMA kernel and the fused SPADE kernel
-    from deepsee_amd import lib as _L
-    ops.PROFILE = {}
-    ops.PROFILE_BYTES.clear()
-    calls_before = _L.CALLS
-    step()
-    torch.cuda.synchronize()
-    capi_calls_per_step = _L.CALLS - calls_before
-    prof, ops.PROFILE = ops.PROFILE, None
-    kernels = {}
-    for name, recs in prof.items():
-        ms = sum(s.elapsed_time(e) for s, e, _ in recs)
-        kernels[name] = {"launches": len(recs), "ms": ms, "tflop": sum(f for _, _, f in recs) / 1e12,
-                         "gb": ops.PROFILE_BYTES.get(name, 0.0) / 1e9}
-    fused_is_r3 = "spade_fused_fwd" in kernels
-    fused = kernels.pop("spade_fused_fwd", None) or kernels.pop("spade_modulate_fused", None)
-    norm_fwd = {k: kernels.pop(k) for k in list(kernels) if k.startswith("norm_forward@")}
-    conv_fwd = {k: kernels.pop(k) for k in list(kernels) if k.startswith("conv_forward@")}
-    dom = max(kernels, key=lambda k: kernels[k]["ms"])
-    kd = kernels[dom]
-    tf = kd["tflop"] / (kd["ms"] / 1e3)
-    gbps = kd["gb"] / (kd["ms"] / 1e3) if kd["gb"] else 0.0
-    peak = kernel_peak(dom)
-    f_mfma, f_hbm = tf / peak, gbps / HBM_PEAK_GBPS
-    mfma_ms = sum(k["ms"] for k in kernels.values())
+    # ---- --full: one extra instrumented step: per-launch HIP events around every MFMA kernel and the fused SPADE kernel
+    fused, fused_is_r3, norm_fwd, conv_fwd = None, False, {}, {}
+    if args.full:
+        from deepsee_amd import lib as _L
+        ops.PROFILE = {}
+        ops.PROFILE_BYTES.clear()
+        calls_before = _L.CALLS
+        step()
+        torch.cuda.synchronize()
+        capi_calls_per_step = _L.CALLS - calls_before
+        prof, ops.PROFILE = ops.PROFILE, None
+        kernels = {}
+        for name, recs in prof.items():
+            ms = sum(s.elapsed_time(e) for s, e, _ in recs)
+            kernels[name] = {"launches": len(recs), "ms": ms, "tflop": sum(f for _, _, f in recs) / 1e12,
+                             "gb": ops.PROFILE_BYTES.get(name, 0.0) / 1e9}
+        fused_is_r3 = "spade_fused_fwd" in kernels
+        fused = kernels.pop("spade_fused_fwd", None) or kernels.pop("spade_modulate_fused", None)
+        norm_fwd = {k: kernels.pop(k) for k in list(kernels) if k.startswith("norm_forward@")}
+        conv_fwd = {k: kernels.pop(k) for k in list(kernels) if k.startswith("conv_forward@")}
+        dom = max(kernels, key=lambda k: kernels[k]["ms"])
+        kd = kernels[dom]
+        tf = kd["tflop"] / (kd["ms"] / 1e3)
+        gbps = kd["gb"] / (kd["ms"] / 1e3) if kd["gb"] else 0.0
+        peak = kernel_peak(dom)
+        f_mfma, f_hbm = tf / peak, gbps / HBM_PEAK_GBPS
+        mfma_ms = sum(k["ms"] for k in kernels.values())
 
     base_plan = tm.sr_model.plan
 
@@ -473,7 +485,7 @@ def main():
         return {"value": n / dt, "unit": "img/s", "ms_per_step": dt * 1e3, "steps": 3, "note": note}
 
     f32_only = bf16x3 = None
-    if world == 1 and base_plan.gemm_split and not args.no_f32_run and headline and not base_plan.half:
+    if args.full and world == 1 and base_plan.gemm_split and not args.no_f32_run and headline and not base_plan.half:
         f32_only = short_run("same step, Winograd-domain GEMMs on v_mfma_f32_32x32x2_f32 instead of split operands",
                              gemm_split=False)
         if base_plan.gemm_f16x2:
@@ -483,7 +495,7 @@ def main():
         tm.sr_model.plan = base_plan
         tm.use_graphs = not args.no_graphs
 
-    dp = dp_report(tm, step, fence, world, rank, n, dev, elapsed_local, elapsed, args.steps) if world > 1 else None
+    dp = dp_report(tm, step, fence, world, rank, n, dev, elapsed_local, elapsed, args.steps) if args.full and world > 1 else None
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -507,40 +519,41 @@ def main():
             "bf16x3": "fp32 storage and accumulation; Winograd-domain GEMMs from exact 3-term bf16 operand splits (6 bf16 "
                       "MFMA products)",
             "f32": "fp32 (v_mfma_f32_32x32x2_f32)"}[kind]
-        traffic, traffic_src = pmc_traffic(dom)
-        # a kernel below half of BOTH datasheet rooflines is bound by neither of them.  Round 6 measured what it IS bound by: the
-        # socket power cap (profiles/r06_gemm_ablation.md) -- `power` below prices it against the MFMA rate that cap allows
-        split_products = round(F16_MFMA_PEAK_TFLOPS / peak) if peak > 200 else 0
-        power_peak = F16_MFMA_POWER_CAP_TFLOPS / split_products if split_products else None
-        # (measured for the Winograd-domain GEMM families; a direct-convolution kernel that ends up dominant -- configs[4] at N = 1 in
-        # the 16-bit mode -- runs at 2.3-2.45 GHz and is latency / issue bound)
-        if not dom.startswith("winograd"):
-            power_peak = None
-        bound = ("neither datasheet roofline: socket power cap" if (max(f_mfma, f_hbm) < 0.5 and power_peak) else
-                 ("neither (issue/latency)" if max(f_mfma, f_hbm) < 0.5 else ("mfma" if f_mfma >= f_hbm else "hbm")))
-        roof = {"bound": bound, "closer_to": "mfma" if f_mfma >= f_hbm else "hbm", "kernel": dom,
-                "achieved": tf if f_mfma >= f_hbm else gbps, "peak": peak if f_mfma >= f_hbm else HBM_PEAK_GBPS,
-                "unit": "TFLOP/s" if f_mfma >= f_hbm else "GB/s", "frac": max(f_mfma, f_hbm),
-                "traffic": traffic, "traffic_source": traffic_src,
-                "mfma": {"achieved_tflops_fp32_equiv": tf, "peak": peak, "frac": f_mfma,
-                         "peak_note": "%.1f dense fp16/bf16 MFMA TFLOP/s / %d products per fp32 multiply-add"
-                                      % (F16_MFMA_PEAK_TFLOPS, round(F16_MFMA_PEAK_TFLOPS / peak)) if peak > 200
-                         else "v_mfma_f32 dense peak"},
-                "hbm": {"achieved_gbps_algorithmic": gbps, "peak": HBM_PEAK_GBPS, "frac": f_hbm},
-                "power": None if not power_peak else {
-                    "socket_cap_w": 1400, "mfma_only_tflops_under_cap_fp16_random_operands": F16_MFMA_POWER_CAP_TFLOPS,
-                    "peak_fp32_equiv_under_cap": power_peak, "frac_of_power_capped_peak": tf / power_peak,
-                    "source": "profiles/r06_mfma_power_cap.txt (MFMAs only, operands in registers, rocm-smi beside it), "
-                              "profiles/r06_gemm_ablation.md (this kernel back to back: 1 378-1 403 W, 1.54 GHz)"},
-                "launches_per_step": kd["launches"], "avg_launch_ms": kd["ms"] / kd["launches"],
-                "algorithmic_gb_per_launch": (kd["gb"] / kd["launches"]) or None,
-                "algorithmic_tflop_per_step": kd["tflop"],
-                "mfma_kernels_ms_per_step": mfma_ms,
-                "all_mfma_kernels": {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
-                                         "tflops": round(v["tflop"] / (v["ms"] / 1e3), 2),
-                                         "frac": round(v["tflop"] / (v["ms"] / 1e3) / kernel_peak(k), 3),
-                                         "gbps": round(v["gb"] / (v["ms"] / 1e3), 1) if v["gb"] else None}
-                                     for k, v in kernels.items()}}
+        if args.full:
+            traffic, traffic_src = pmc_traffic(dom)
+            # a kernel below half of BOTH datasheet rooflines is bound by neither of them.  Round 6 measured what it IS bound by:
+            # the socket power cap (profiles/r06_gemm_ablation.md) -- `power` below prices it against the MFMA rate that cap allows
+            split_products = round(F16_MFMA_PEAK_TFLOPS / peak) if peak > 200 else 0
+            power_peak = F16_MFMA_POWER_CAP_TFLOPS / split_products if split_products else None
+            # (measured for the Winograd-domain GEMM families; a direct-convolution kernel that ends up dominant -- configs[4] at
+            # N = 1 in the 16-bit mode -- runs at 2.3-2.45 GHz and is latency / issue bound)
+            if not dom.startswith("winograd"):
+                power_peak = None
+            bound = ("neither datasheet roofline: socket power cap" if (max(f_mfma, f_hbm) < 0.5 and power_peak) else
+                     ("neither (issue/latency)" if max(f_mfma, f_hbm) < 0.5 else ("mfma" if f_mfma >= f_hbm else "hbm")))
+            roof = {"bound": bound, "closer_to": "mfma" if f_mfma >= f_hbm else "hbm", "kernel": dom,
+                    "achieved": tf if f_mfma >= f_hbm else gbps, "peak": peak if f_mfma >= f_hbm else HBM_PEAK_GBPS,
+                    "unit": "TFLOP/s" if f_mfma >= f_hbm else "GB/s", "frac": max(f_mfma, f_hbm),
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "mfma": {"achieved_tflops_fp32_equiv": tf, "peak": peak, "frac": f_mfma,
+                             "peak_note": "%.1f dense fp16/bf16 MFMA TFLOP/s / %d products per fp32 multiply-add"
+                                          % (F16_MFMA_PEAK_TFLOPS, round(F16_MFMA_PEAK_TFLOPS / peak)) if peak > 200
+                             else "v_mfma_f32 dense peak"},
+                    "hbm": {"achieved_gbps_algorithmic": gbps, "peak": HBM_PEAK_GBPS, "frac": f_hbm},
+                    "power": None if not power_peak else {
+                        "socket_cap_w": 1400, "mfma_only_tflops_under_cap_fp16_random_operands": F16_MFMA_POWER_CAP_TFLOPS,
+                        "peak_fp32_equiv_under_cap": power_peak, "frac_of_power_capped_peak": tf / power_peak,
+                        "source": "profiles/r06_mfma_power_cap.txt (MFMAs only, operands in registers, rocm-smi beside it), "
+                                  "profiles/r06_gemm_ablation.md (this kernel back to back: 1 378-1 403 W, 1.54 GHz)"},
+                    "launches_per_step": kd["launches"], "avg_launch_ms": kd["ms"] / kd["launches"],
+                    "algorithmic_gb_per_launch": (kd["gb"] / kd["launches"]) or None,
+                    "algorithmic_tflop_per_step": kd["tflop"],
+                    "mfma_kernels_ms_per_step": mfma_ms,
+                    "all_mfma_kernels": {k: {"launches": v["launches"], "ms": round(v["ms"], 3),
+                                             "tflops": round(v["tflop"] / (v["ms"] / 1e3), 2),
+                                             "frac": round(v["tflop"] / (v["ms"] / 1e3) / kernel_peak(k), 3),
+                                             "gbps": round(v["gb"] / (v["ms"] / 1e3), 1) if v["gb"] else None}
+                                         for k, v in kernels.items()}}
         losses = {k: float(v.detach()) for k, v in tm.get_latest_losses().items()}
         if not all(math.isfinite(v) for v in losses.values()):
             raise RuntimeError("bench.py: non-finite losses after the timed steps %r -- the measurement is void" % losses)
@@ -559,8 +572,9 @@ def main():
                                        "independent_32x_512": "independent 32x 16->512"}[args.config], n, args.dtype, ref),
                        "global_batch": n * world, "parallelism": "dp%d" % world,
                        "losses": losses},
-            "roofline": roof,
         }
+        if args.full:
+            out["roofline"] = roof
         # whole-model rate in the reference's dense-convolution FLOP count (conv MACs x 2 of the reference's
         # graph per image and iteration); the Winograd layers execute 2.25x fewer multiplies than that
         dense = {"independent_8x_256": 7.15, "guided_8x_256": 7.15, "independent_32x_512": 22.6}[args.config]
@@ -569,9 +583,11 @@ def main():
                               "note": "N * F_iter / t_iter with SURVEY 8(d)'s F_iter; exceeds the fp32 MFMA peak because "
                                       "the wide layers run on the fp16 matrix cores in the Winograd domain"}
         out["peak_hbm_gb"] = round(torch.cuda.max_memory_allocated(dev) / 1e9, 2)   # of 288 GB (kept V / M tensors included)
-        out["launches_per_step"] = {"c_abi_entry_points": capi_calls_per_step,
-                                    "note": "dsee_* calls of one eager G + D step (an entry point is 1-3 kernel launches); the "
-                                            "rocprofv3 count of ALL kernels incl. ATen glue is in profiles/r06_kernel_stats_all.md"}
+        if args.full:
+            out["launches_per_step"] = {"c_abi_entry_points": capi_calls_per_step,
+                                        "note": "dsee_* calls of one eager G + D step (an entry point is 1-3 kernel launches); "
+                                                "the rocprofv3 count of ALL kernels incl. ATen glue is in "
+                                                "profiles/r06_kernel_stats_all.md"}
         out["host_enqueue_ms_per_step"] = host / args.steps * 1e3
         out["host_ms_per_step_incl_queue_backpressure"] = sum(host_steps) / args.steps * 1e3
         out["hip_graphs"] = {"enabled": bool(tm.use_graphs), "captured": sorted("/".join(map(str, k[:3])) for k in tm._graphs),
@@ -663,7 +679,7 @@ def main():
             out["f32_mfma_only"] = f32_only
         if bf16x3:
             out["bf16x3_exact"] = bf16x3
-        if world == 1 and not args.no_cpu_baseline and headline and not base_plan.half:
+        if args.full and world == 1 and not args.no_cpu_baseline and headline and not base_plan.half:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_bs, args.cpu_baseline_iters)
         print(json.dumps(out))
     if world > 1:

@@ -5,13 +5,13 @@
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/evidence; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_fp32.json 2> $O/bench_fp32.err
-python bench.py --steps 20 --warmup 5 --dtype fp16 > $O/bench_fp16.json 2>/dev/null
-python bench.py --steps 10 --warmup 3 --dtype fp16 --plan half_norms=False > $O/bench_fp16_two_term_norms.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --config guided_8x_256 --no-f32-run --no-cpu-baseline > $O/bench_guided_8x_256.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --config independent_32x_512 --no-f32-run --no-cpu-baseline > $O/bench_independent_32x_512.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --config independent_32x_512 --dtype fp16 > $O/bench_independent_32x_512_fp16.json 2>/dev/null
-python bench.py --steps 8 --warmup 2 --no-graphs --no-f32-run --no-cpu-baseline > $O/bench_no_graphs.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_fp32.json 2> $O/bench_fp32.err
+python bench.py --full --steps 20 --warmup 5 --dtype fp16 > $O/bench_fp16.json 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 --dtype fp16 --plan half_norms=False > $O/bench_fp16_two_term_norms.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --config guided_8x_256 --no-f32-run --no-cpu-baseline > $O/bench_guided_8x_256.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --config independent_32x_512 --no-f32-run --no-cpu-baseline > $O/bench_independent_32x_512.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --config independent_32x_512 --dtype fp16 > $O/bench_independent_32x_512_fp16.json 2>/dev/null
+python bench.py --full --steps 8 --warmup 2 --no-graphs --no-f32-run --no-cpu-baseline > $O/bench_no_graphs.json 2>/dev/null
 python tools/step_functions.py > $O/step_functions.txt 2>&1
 python tools/exp/mall_probe.py > $O/mall_probe.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
@@ -25,5 +25,5 @@ python $R/tools/pmc_traffic.py /tmp/pmc_FETCH_SIZE/*counter_collection.csv /tmp/
 for c in FETCH_SIZE WRITE_SIZE; do rocprofv3 --kernel-trace --pmc $c -d /tmp/pmc16_$c -o p --output-format csv -- python $R/bench.py --dtype fp16 --steps 2 --warmup 1 --no-graphs > /dev/null 2>&1; done
 python $R/tools/pmc_traffic.py /tmp/pmc16_FETCH_SIZE/*counter_collection.csv /tmp/pmc16_WRITE_SIZE/*counter_collection.csv > $O/pmc_traffic_fp16.json
 cd $R
-python bench.py --steps 3 --warmup 2 --no-f32-run --cpu-baseline-bs 8 > $O/bench_cpu_baseline_bs8.json 2>/dev/null
+python bench.py --full --steps 3 --warmup 2 --no-f32-run --cpu-baseline-bs 8 > $O/bench_cpu_baseline_bs8.json 2>/dev/null
 ls -la $O

@@ -5,16 +5,16 @@
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/evidence; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_fp32.json 2> $O/bench_fp32.err
-python bench.py --steps 20 --warmup 5 --dtype fp16 > $O/bench_fp16.json 2>/dev/null
-python bench.py --steps 10 --warmup 3 --dtype fp16 --plan half_norms=False > $O/bench_fp16_two_term_norms.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --config guided_8x_256 --no-f32-run --no-cpu-baseline > $O/bench_guided_8x_256.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --config independent_32x_512 --no-f32-run --no-cpu-baseline > $O/bench_independent_32x_512.json 2>/dev/null
-python bench.py --steps 5 --warmup 2 --config independent_32x_512 --dtype fp16 > $O/bench_independent_32x_512_fp16.json 2>/dev/null
-python bench.py --steps 8 --warmup 2 --no-graphs --no-f32-run --no-cpu-baseline > $O/bench_no_graphs.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/bench_fp32.json 2> $O/bench_fp32.err
+python bench.py --full --steps 20 --warmup 5 --dtype fp16 > $O/bench_fp16.json 2>/dev/null
+python bench.py --full --steps 10 --warmup 3 --dtype fp16 --plan half_norms=False > $O/bench_fp16_two_term_norms.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --config guided_8x_256 --no-f32-run --no-cpu-baseline > $O/bench_guided_8x_256.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --config independent_32x_512 --no-f32-run --no-cpu-baseline > $O/bench_independent_32x_512.json 2>/dev/null
+python bench.py --full --steps 5 --warmup 2 --config independent_32x_512 --dtype fp16 > $O/bench_independent_32x_512_fp16.json 2>/dev/null
+python bench.py --full --steps 8 --warmup 2 --no-graphs --no-f32-run --no-cpu-baseline > $O/bench_no_graphs.json 2>/dev/null
 # what plan.branch_streams (parallel graph branches: off by default, HIP-runtime segfault) would buy, same box
-python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan branch_streams=True > $O/bench_branch_streams.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline > $O/bench_fp32_again.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan branch_streams=True > $O/bench_branch_streams.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline > $O/bench_fp32_again.json 2>/dev/null
 python tools/step_functions.py > $O/step_functions.txt 2>&1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ev -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-run > $O/bench_under_rocprof.json 2> /dev/null

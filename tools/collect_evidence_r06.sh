@@ -19,21 +19,21 @@ run() {   # run <output file> <command ...>: stdout -> file, non-zero exit or a 
     rm -f "$out.err"
   fi
 }
-run $O/bench_fp32.json python bench.py --steps 20 --warmup 5
-run $O/bench_fp16.json python bench.py --steps 20 --warmup 5 --dtype fp16
-run $O/bench_fp16_two_term_norms.json python bench.py --steps 10 --warmup 3 --dtype fp16 --plan half_norms=False
-run $O/bench_guided_8x_256.json python bench.py --steps 5 --warmup 2 --config guided_8x_256 --no-f32-run --no-cpu-baseline
-run $O/bench_independent_32x_512.json python bench.py --steps 5 --warmup 2 --config independent_32x_512 --no-f32-run --no-cpu-baseline
-run $O/bench_independent_32x_512_fp16.json python bench.py --steps 5 --warmup 2 --config independent_32x_512 --dtype fp16
-run $O/bench_no_graphs.json python bench.py --steps 8 --warmup 2 --no-graphs --no-f32-run --no-cpu-baseline
+run $O/bench_fp32.json python bench.py --full --steps 20 --warmup 5
+run $O/bench_fp16.json python bench.py --full --steps 20 --warmup 5 --dtype fp16
+run $O/bench_fp16_two_term_norms.json python bench.py --full --steps 10 --warmup 3 --dtype fp16 --plan half_norms=False
+run $O/bench_guided_8x_256.json python bench.py --full --steps 5 --warmup 2 --config guided_8x_256 --no-f32-run --no-cpu-baseline
+run $O/bench_independent_32x_512.json python bench.py --full --steps 5 --warmup 2 --config independent_32x_512 --no-f32-run --no-cpu-baseline
+run $O/bench_independent_32x_512_fp16.json python bench.py --full --steps 5 --warmup 2 --config independent_32x_512 --dtype fp16
+run $O/bench_no_graphs.json python bench.py --full --steps 8 --warmup 2 --no-graphs --no-f32-run --no-cpu-baseline
 # same-box A/B of this round's plan switches (each against bench_fp32_again.json)
-run $O/bench_fp32_again.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline
-run $O/bench_ab_gemm_w8.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan gemm_w4=False
-run $O/bench_ab_dgrad_gather.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan dgrad_s2_parity=False
-run $O/bench_ab_absmax_passes.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan conv_amax_out=False
-run $O/bench_ab_conv_igemm_no_halo.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan conv_halo_f16=False
-run $O/bench_ab_onehot_wgrad_valu.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan onehot_wgrad_mfma=False
-run $O/bench_ab_fused_w4.json python bench.py --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan fused_w4=True
+run $O/bench_fp32_again.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline
+run $O/bench_ab_gemm_w8.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan gemm_w4=False
+run $O/bench_ab_dgrad_gather.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan dgrad_s2_parity=False
+run $O/bench_ab_absmax_passes.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan conv_amax_out=False
+run $O/bench_ab_conv_igemm_no_halo.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan conv_halo_f16=False
+run $O/bench_ab_onehot_wgrad_valu.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan onehot_wgrad_mfma=False
+run $O/bench_ab_fused_w4.json python bench.py --full --steps 20 --warmup 5 --no-f32-run --no-cpu-baseline --plan fused_w4=True
 run $O/step_shapes.txt python tools/step_shapes.py
 run $O/step_functions.txt python tools/step_functions.py 60
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 set -u
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/evidence; mkdir -p $O
 cd $R
-python bench.py --steps 20 --warmup 5 > $O/bench_fp32.json 2> $O/bench_fp32.err
+python bench.py --full --steps 20 --warmup 5 > $O/bench_fp32.json 2> $O/bench_fp32.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d /tmp/prof -o ev -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-run > $O/bench_under_rocprof.json 2> /dev/null
 python $R/tools/rocpd_summary.py /tmp/prof/ev_results.db > $O/kernel_stats.md
