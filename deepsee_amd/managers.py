@@ -1,8 +1,13 @@
-"""BaseManager / TrainerManager — same method surface as the reference's managers/base_manager.py and
-managers/trainer_manager.py, driving the HIP-backed SRModel."""
+"""BaseManager / TrainerManager / InferenceManager — same method surface as the reference's managers/base_manager.py,
+managers/trainer_manager.py and managers/inference_manager.py, driving the HIP-backed SRModel."""
+import os
+import sys
+import traceback
+
 import torch
 
 from . import ops
+from .metrics import MetricsEvaluator
 from .sr_model import SRModel
 
 
@@ -328,6 +333,68 @@ class TrainerManager(BaseManager):
                 g["lr"] = new_lr_g
             print("update learning rate: %f -> %f" % (self.old_lr, new_lr))
             self.old_lr = new_lr
+
+
+class InferenceManager(BaseManager):
+    """inference_manager.py:22-147, the validation loop train.py runs every `evaluation_freq` samples: `run(model, dataloader)`
+    puts the model into eval mode, generates up to num_samples // batchSize + 1 batches with mode "inference", scores every
+    batch on the device (PSNR / SSIM / MS-SSIM / RMSE: deepsee_amd.metrics) and returns one OrderedDict.
+
+    What differs from the reference: the result has no "FID" key and no LPIPS entries (Inception / AlexNet weights are out of
+    scope, see deepsee_amd.metrics), and save_images=True raises NotImplementedError (the reference's writer needs cv2 and its
+    HTML visualizer).  Builds no model: `model` is the SRModel of a live TrainerManager (between training steps, with or
+    without hipGraphs -- the eval-mode forward advances neither the normalisation layers' running statistics, the spectral-norm
+    vectors, the branch coins nor the Philox epoch, so the training run continues bit-identically) or a standalone one."""
+
+    def __init__(self, opt, num_samples, write_details=False, folder_out=None, save_images=False, cuda=True):
+        super().__init__(opt, create_model=False)
+        if save_images:
+            raise NotImplementedError("InferenceManager(save_images=True): the image writer (cv2 / HTML visualizer in the "
+                                      "reference) is not part of this build; take out['fake_image'] from run_batch()")
+        self.num_samples = num_samples
+        self.batch_size = opt.batchSize
+        self.write = write_details
+        self.save_image = False
+        self.folder_out = folder_out
+        if self.write:
+            os.makedirs(self.folder_out, exist_ok=True)
+        self.metrics = MetricsEvaluator(write_details, folder_out, ms_ssim=True)
+        self.cuda = cuda                   # (kept for the signature: the metrics always run where the images are)
+        self.skipped_samples = 0           # of the last run()
+
+    def run_batch(self, data, model):
+        data = super().preprocess(data, from_dataloader=True)
+        with torch.no_grad():
+            return model(data, "inference")
+
+    def run(self, model, dataloader):
+        dataloader = iter(dataloader)
+        model = model.eval()
+        num_batches = self.num_samples // self.batch_size + 1
+        self.skipped_samples = 0
+        try:
+            for i in range(num_batches):
+                if i > 0 and i * self.batch_size % 500 < self.batch_size:
+                    print("\rCurrent result: {}".format(self.metrics.get_result()))
+                try:
+                    data_i = next(dataloader)
+                    out = self.run_batch(data_i, model)
+                    # (no .detach() here: it would drop the native-layout tag of image_hr; the metrics detach what they read)
+                    self.metrics.collect_samples(out["fake_image"], out["image_hr"], data_i.get("path"))
+                except ValueError:
+                    print(traceback.format_exc())
+                    print(sys.exc_info()[0])
+                    print("Value error. Skipping sample...")
+                    self.skipped_samples += 1
+                except StopIteration:
+                    print("StopIteration raised. Finishing up...")
+                    break
+            result = self.metrics.get_result()
+        finally:
+            self.metrics.clear()
+            model.train()
+        print("Evaluation finished. Total number of samples skipped: {}".format(self.skipped_samples))
+        return result
 
 
 import weakref as _weakref

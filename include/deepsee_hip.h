@@ -234,6 +234,19 @@ int dsee_wino43_input_adjoint_amax_f16(const void* dV16, float* dx, int N, int H
 size_t dsee_psnr_ssim_workspace(int N, int H, int W);
 int dsee_psnr_ssim(const float* fake, const float* real, int N, int H, int W, int Cs, double* workspace,
                    size_t workspace_bytes, double* out, hipStream_t stream);
+/* MS-SSIM per image, = msssim(fake255, real255, size_average=True, val_range=255) as MetricsEvaluator.collect_samples calls it
+ * per sample (evaluator/evaluation.py:114,125-127 -> evaluator/ssim.py:24-118), on the same fp32 NHWC inputs (channels 0..2):
+ * x -> (x + 1) * 127.5, neither quantised nor clipped; 5 levels, level l+1 = 2x2 / stride-2 average of level l (floor sizes);
+ * per level a k x k window, k = min(11, h, w), = the outer product of the normalised sigma-1.5 Gaussian ROUNDED TO fp32
+ * (create_window returns .float(): the window is not separable, and its weights do not sum to 1), valid convolution of
+ * x, y, x^2, y^2, xy in float64; means of the SSIM map and of cs = (2 s12 + C2) / (s11 + s22 + C2) over positions and channels.
+ * out [N][11] doubles = {prod_{l<4} (cs_l^w_l * sim_4^w_4), cs_0..cs_4, sim_0..sim_4}, w = the reference's fp32 weights
+ * (ssim.py:117 multiplies each of the four cs factors by sim_4^w_4, so that term enters with the 4th power: kept); a
+ * negative cs_l (l < 4) or sim_4 gives NaN as in the reference (nothing is clamped).  workspace from dsee_ms_ssim_workspace;
+ * deterministic (no atomics), nothing allocated, no stream synchronisation.  H, W >= 16 (below, a pyramid level is empty). */
+size_t dsee_ms_ssim_workspace(int N, int H, int W);
+int dsee_ms_ssim(const float* fake, const float* real, int N, int H, int W, int Cs, double* workspace,
+                 size_t workspace_bytes, double* out, hipStream_t stream);
 /* Test hook (no reference counterpart): fills the LDS of every CU with NaN bit patterns, so that a pipelined kernel
  * launched next shows a read of a not-yet-landed LDS stage as NaN instead of as stale but plausible data.  sink: one float. */
 int dsee_selftest_lds_poison(float* sink, hipStream_t stream);
