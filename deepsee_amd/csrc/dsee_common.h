@@ -196,6 +196,20 @@ __host__ __device__ constexpr float dsee_dm_rowr(int i) { return (i == 0 || i ==
 __host__ __device__ constexpr float dsee_dm_posf(int xi) { return dsee_dm_rowf(xi / 6) * dsee_dm_rowf(xi % 6); }
 __host__ __device__ constexpr float dsee_dm_posr(int xi) { return dsee_dm_rowr(xi / 6) * dsee_dm_rowr(xi % 6); }
 
+// Weights of the four taps around a source coordinate with fraction t (F.interpolate mode='bicubic': A = -0.75); shared by
+// dsee_bicubic_down (elementwise.hip) and dsee_bicubic_up (visuals.hip)
+__device__ __forceinline__ void cubic_coeffs(float t, float (&w)[4]) {
+  const float A = -0.75f;  // PyTorch bicubic
+  float x = t + 1.f;
+  w[0] = ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+  x = t;
+  w[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+  x = 1.f - t;
+  w[2] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+  x = 2.f - t;
+  w[3] = ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+}
+
 // Index arithmetic of the NHWC walkers.  The ISA has no integer divide: a 64-bit division by a run-time value compiles to ~150
 // instructions with branches, and three of them per float4 item (n, h, w, channel quad) left up_noise / sumpool instruction-bound
 // at ~2 TB/s.  Item counts fit 32 bits (the hosts check), and a 32-bit unsigned division is ~20 instructions.

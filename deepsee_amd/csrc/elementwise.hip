@@ -330,18 +330,6 @@ __global__ void label_u8_prepare_kernel(const uint8_t* __restrict__ lab, const u
   }
 }
 
-__device__ __forceinline__ void cubic_coeffs(float t, float (&w)[4]) {
-  const float A = -0.75f;  // PyTorch bicubic
-  float x = t + 1.f;
-  w[0] = ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
-  x = t;
-  w[1] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-  x = 1.f - t;
-  w[2] = ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
-  x = 2.f - t;
-  w[3] = ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
-}
-
 // F.interpolate(mode='bicubic', align_corners=False) + clamp(-1,1); NHWC in (Cs_in) -> NHWC out (Cs_out), 3 channels
 __global__ void bicubic_down_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int S,
                                     int cs_in, int cs_out) {

@@ -342,15 +342,16 @@ class InferenceManager(BaseManager):
 
     What differs from the reference: the result has no "FID" key and no LPIPS entries (Inception / AlexNet weights are out of
     scope, see deepsee_amd.metrics), and save_images=True raises NotImplementedError (the reference's writer needs cv2 and its
-    HTML visualizer).  Builds no model: `model` is the SRModel of a live TrainerManager (between training steps, with or
+    HTML visualizer): images are written with run(..., save_to=<folder>) instead (deepsee_amd.visuals), and
+    run(..., mode="baseline") scores the bicubic upsampling.  Builds no model: `model` is the SRModel of a live TrainerManager (between training steps, with or
     without hipGraphs -- the eval-mode forward advances neither the normalisation layers' running statistics, the spectral-norm
     vectors, the branch coins nor the Philox epoch, so the training run continues bit-identically) or a standalone one."""
 
     def __init__(self, opt, num_samples, write_details=False, folder_out=None, save_images=False, cuda=True):
         super().__init__(opt, create_model=False)
         if save_images:
-            raise NotImplementedError("InferenceManager(save_images=True): the image writer (cv2 / HTML visualizer in the "
-                                      "reference) is not part of this build; take out['fake_image'] from run_batch()")
+            raise NotImplementedError("InferenceManager(save_images=True): the reference's cv2 / HTML visualizer route is not "
+                                      "part of this build; write the images with run(model, dataloader, save_to=<folder>)")
         self.num_samples = num_samples
         self.batch_size = opt.batchSize
         self.write = write_details
@@ -362,25 +363,46 @@ class InferenceManager(BaseManager):
         self.cuda = cuda                   # (kept for the signature: the metrics always run where the images are)
         self.skipped_samples = 0           # of the last run()
 
-    def run_batch(self, data, model):
+    def run_batch(self, data, model, mode="inference"):
+        """One batch through `model` in mode "inference" or "baseline" (the bicubic image every SR table is compared against).
+        Returns the inference mode's dict either way: the baseline's reference keys (input_label, image_downsized, image_full)
+        are mapped back, so that the metrics and the image writer read the same entries."""
+        if mode not in ("inference", "baseline"):
+            raise ValueError("InferenceManager: mode is 'inference' or 'baseline', got %r" % (mode,))
         data = super().preprocess(data, from_dataloader=True)
         with torch.no_grad():
-            return model(data, "inference")
+            out = model(data, mode)
+        if mode == "baseline":
+            out = dict(data, input_semantics=out["input_label"], image_lr=out["image_downsized"], image_hr=out["image_full"],
+                       fake_image=out["fake_image"])
+        return out
 
-    def run(self, model, dataloader):
+    def run(self, model, dataloader, mode="inference", save_to=None):
+        """mode="baseline" scores the bicubic upsampling instead of the generator's image.  save_to=<folder> also writes every
+        batch's images there (deepsee_amd.visuals.ImageWriter: <folder>/<key>/<name>.png and <folder>/combined/<name>.png,
+        converted on the device, encoded on a host thread while the next batch is generated)."""
+        if mode not in ("inference", "baseline"):
+            raise ValueError("InferenceManager.run: mode is 'inference' or 'baseline', got %r" % (mode,))
         dataloader = iter(dataloader)
         model = model.eval()
         num_batches = self.num_samples // self.batch_size + 1
         self.skipped_samples = 0
+        writer = None
+        if save_to is not None:
+            from .visuals import ImageWriter
+            writer = ImageWriter(save_to)
         try:
             for i in range(num_batches):
                 if i > 0 and i * self.batch_size % 500 < self.batch_size:
                     print("\rCurrent result: {}".format(self.metrics.get_result()))
                 try:
                     data_i = next(dataloader)
-                    out = self.run_batch(data_i, model)
+                    out = self.run_batch(data_i, model, mode)
                     # (no .detach() here: it would drop the native-layout tag of image_hr; the metrics detach what they read)
                     self.metrics.collect_samples(out["fake_image"], out["image_hr"], data_i.get("path"))
+                    if writer is not None:
+                        n = out["fake_image"].shape[0]
+                        writer.submit(out, data_i.get("path") or ["%06d" % (i * self.batch_size + b) for b in range(n)])
                 except ValueError:
                     print(traceback.format_exc())
                     print(sys.exc_info()[0])
@@ -389,10 +411,15 @@ class InferenceManager(BaseManager):
                 except StopIteration:
                     print("StopIteration raised. Finishing up...")
                     break
+            if writer is not None:
+                writer, w = None, writer
+                w.close()                  # waits for the files; re-raises what the writer thread raised
             result = self.metrics.get_result()
         finally:
             self.metrics.clear()
             model.train()
+            if writer is not None:         # (the loop raised: stop the thread, keep the loop's exception)
+                writer.close(reraise=False)
         print("Evaluation finished. Total number of samples skipped: {}".format(self.skipped_samples))
         return result
 

@@ -202,6 +202,17 @@ def bicubic_down(img_nhwc, size):
     return y
 
 
+def bicubic_up(img_nhwc, h, w, clamp=True):
+    """F.interpolate(x, (h, w), mode='bicubic')[.clamp(-1, 1)] of a square native image [N,S,S,cs] -> [N,h,w,4] (the 'baseline'
+    every SR table is compared against, sr_model.py:109-115)."""
+    n, s, s2, cs = img_nhwc.shape
+    assert s == s2, "square source expected, got %s" % (tuple(img_nhwc.shape),)
+    y = new(n, h, w, 4)
+    L.call("bicubic_up", img_nhwc.contiguous(), y, n, s, h, w, cs, 4, int(bool(clamp)))
+    y.dsee_layout = "nhwc"
+    return y
+
+
 class Labels:
     """uint8 HR label map + the shift for a given resolution (nearest resize as index math)."""
 

@@ -178,6 +178,12 @@ class SRModel(nn.Module):
                 fake = self.netSR(d["image_lr"], d["labels"], style, self.noise, self.training)
             data["fake_image"] = ops.to_nchw(fake, 3)
             return {k: v for k, v in data.items() if v is not None}
+        elif mode == "baseline":
+            # sr_model.py:109-115: bicubic upsampling of the LR image to the HR size, clamped -- no network, no noise, no coins
+            hr = d["image_hr"]
+            up = ops.bicubic_up(d["image_lr"], hr.shape[1], hr.shape[2], clamp=True)
+            return OrderedDict([("input_label", data.get("input_semantics")), ("image_downsized", data.get("image_lr")),
+                                ("fake_image", ops.to_nchw(up, 3)), ("image_full", data.get("image_hr"))])
         else:
             raise ValueError("|mode| is invalid")
 

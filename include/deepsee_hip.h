@@ -247,6 +247,34 @@ int dsee_psnr_ssim(const float* fake, const float* real, int N, int H, int W, in
 size_t dsee_ms_ssim_workspace(int N, int H, int W);
 int dsee_ms_ssim(const float* fake, const float* real, int N, int H, int W, int Cs, double* workspace,
                  size_t workspace_bytes, double* out, hipStream_t stream);
+/* Output side of the device pipeline (util/util.py:44-158,245-311 tensor2im / tensor2label / Colorize, util/visualizer.py:181-215
+ * save_images_only): what leaves the card is what the PNG files hold, packed 3-byte RGB pixels.  Every kernel writes a
+ * W x H window of a destination described by (dst, dst_image_stride, dst_row_stride, dst_x_offset): pixel (n, y, x) goes to
+ * dst + n * dst_image_stride + y * dst_row_stride + 3 * (dst_x_offset + x) (strides in bytes, the offset in pixels), so that a
+ * per-key image and one column of a side-by-side strip are the same call with another destination.  Bytes outside the window
+ * are not touched.  (When dst and both strides are multiples of 4, four pixels leave as three 4-byte stores; otherwise and at
+ * the ragged ends of a row, bytes.)
+ *
+ * dsee_image_to_u8: fp32 image -> uint8.  x is NHWC [N][H][W][cs] (nchw = 0, cs >= 3: the native RGB0 layout) or NCHW
+ * [N][3][H][W] (nchw != 0, cs ignored).  normalize != 0: u = (x + 1) / 2 * 255, else u = x * 255; then clip to [0, 255] and
+ * truncate -- fp32, one rounding per operation, in that order: bit-identical to numpy's tensor2im. */
+int dsee_image_to_u8(const float* x, uint8_t* dst, int N, int H, int W, int cs, int nchw, int normalize,
+                     long dst_image_stride, long dst_row_stride, int dst_x_offset, hipStream_t stream);
+/* dsee_label_colorize: uint8 index map [N][H][W] + colour table [n_colors][3] uint8 (device) -> RGB; an index >= n_colors
+ * gives (0, 0, 0), as Colorize leaves pixels no table row matches.  n_colors <= 256. */
+int dsee_label_colorize(const uint8_t* labels, const uint8_t* table, int n_colors, uint8_t* dst, int N, int H, int W,
+                        long dst_image_stride, long dst_row_stride, int dst_x_offset, hipStream_t stream);
+/* dsee_bicubic_up: F.interpolate(x, (H, W), mode='bicubic') with align_corners=False (A = -0.75, border indices clamped, source
+ * coordinate scale * (dst + 0.5) - 0.5 with scale = S / H resp. S / W in fp32), then clamp(-1, 1) if clamp != 0.  NHWC
+ * [N][S][S][cs_in] -> [N][H][W][cs_out], 3 channels, padding channels of y written as 0.  H, W >= S. */
+int dsee_bicubic_up(const float* x, float* y, int N, int S, int H, int W, int cs_in, int cs_out, int clamp,
+                    hipStream_t stream);
+/* dsee_bilinear_up_u8: uint8 RGB [N][S][S][3] (rows src_row_stride bytes apart, images src_image_stride) -> an H x W window.
+ * Bilinear with half-pixel centres: f = scale * (d + 0.5) - 0.5, scale = S / H resp. S / W, i0 = floor(f), t = f - i0, both
+ * neighbours clamped to [0, S - 1]; top = (1 - tx) p00 + tx p01, bottom likewise, v = (1 - ty) top + ty bottom, every operation
+ * rounded to fp32; result floor(v + 0.5).  (The reference resizes with cv2 here: this definition is the specification.) */
+int dsee_bilinear_up_u8(const uint8_t* src, long src_image_stride, long src_row_stride, int S, uint8_t* dst, int N, int H,
+                        int W, long dst_image_stride, long dst_row_stride, int dst_x_offset, hipStream_t stream);
 /* Test hook (no reference counterpart): fills the LDS of every CU with NaN bit patterns, so that a pipelined kernel
  * launched next shows a read of a not-yet-landed LDS stage as NaN instead of as stale but plausible data.  sink: one float. */
 int dsee_selftest_lds_poison(float* sink, hipStream_t stream);
