@@ -33,6 +33,9 @@ DEFAULTS = dict(
                                  # capturing RCCL operations aborts intermittently in the HIP runtime on ROCm 7.0.2 / RCCL 2.26.6)
     precision="fp32",        # "fp16": one-term scaled-fp16 matrix-core GEMMs + fp16 Winograd-domain products (BASELINE configs[2])
     kernel_plan=None,        # deepsee_amd.plan.KernelPlan, or a dict of its field overrides: which equivalent kernel paths the model takes
+    # explorative inference (options/test_options.py; deepsee_amd.explore)
+    region_idx=None, n_interpolation=5, noise_delta=0.0, noise_dist="normal", dont_merge_fake=False, manipulate_scale=1.0,
+    explore_chunk=8,         # build-only: (image, style variant) pairs per generator pass of an explorative mode
 )
 
 PRESETS = {

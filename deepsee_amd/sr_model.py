@@ -1,7 +1,8 @@
 """SRModel — the model facade of the hot path, same surface as the reference's
 deepsee_models/sr_model.py::SRModel: attributes netSR / netD / netE / opt / model_variant / logs /
 last_encoded_style_is_full / last_encoded_style_is_noisy; forward(data, mode) with modes 'generator', 'encode_only', 'demo',
-'discriminator', 'inference' (anything else raises ValueError like sr_model.py:445-446); create_optimizers(opt);
+'discriminator', 'inference', 'baseline' and the six explorative modes of deepsee_amd.explore.MODES (anything else raises
+ValueError like sr_model.py:445-446); create_optimizers(opt);
 save(epoch) / load_weights().  All activation-space compute runs in libdeepsee_hip.so.
 """
 import math
@@ -13,6 +14,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 
+from . import explore
 from . import lib as L
 from . import networks as N
 from . import ops
@@ -184,8 +186,31 @@ class SRModel(nn.Module):
             up = ops.bicubic_up(d["image_lr"], hr.shape[1], hr.shape[2], clamp=True)
             return OrderedDict([("input_label", data.get("input_semantics")), ("image_downsized", data.get("image_lr")),
                                 ("fake_image", ops.to_nchw(up, 3)), ("image_full", data.get("image_hr"))])
+        elif mode in explore.MODES:
+            # sr_model.py:219-444: the style variants of the batch, one generator pass over all (image, variant) pairs
+            return explore.forward(self, data, d, mode, u8=bool(kwargs.get("u8", False)))
         else:
             raise ValueError("|mode| is invalid")
+
+    def get_noise(self, shape, delta):
+        """sr_model.py:448-457: drawn with torch's CPU generator, then uploaded -- the numbers torch.manual_seed gives the
+        reference."""
+        if self.opt.noise_dist == "normal":
+            noise = torch.randn(shape).clamp(-1, 1) * delta
+        elif self.opt.noise_dist == "uniform":
+            noise = torch.rand(shape).clamp(-1, 1) * delta
+        else:
+            raise ValueError("Invalid noise distribution: {}".format(self.opt.noise_dist))
+        return noise.cuda()
+
+    def encode_with(self, branch, image, labels):
+        """The uncorrupted style matrix of an explicit (image, label map) through an explicit encoder branch ('full' | 'mini';
+        the guided model has the full one only), in eval mode: no coin is flipped, no spectral-norm vector or running statistic
+        advances, and last_encoded_style_is_* keep what the last training forward left."""
+        if self.model_variant == "guided":
+            assert branch == "full", "the guided model has no mini encoder"
+        with torch.no_grad():
+            return self.netE(image, labels, branch, True, self.noise, False)
 
     def load_vgg_state(self, state):
         """Load torchvision's vgg19 weights into the frozen perceptual taps (architecture.py:151-181).  Accepts the

@@ -275,6 +275,26 @@ int dsee_bicubic_up(const float* x, float* y, int N, int S, int H, int W, int cs
  * rounded to fp32; result floor(v + 0.5).  (The reference resizes with cv2 here: this definition is the specification.) */
 int dsee_bilinear_up_u8(const uint8_t* src, long src_image_stride, long src_row_stride, int S, uint8_t* dst, int N, int H,
                         int W, long dst_image_stride, long dst_row_stride, int dst_x_offset, hipStream_t stream);
+/* Explorative inference (sr_model.py:219-444: inference_interpolation, _interpolation_style, _particular_combined,
+ * _particular_full, _reference, _reference_interpolation): the style matrix of every (image b, variant k) pair, and the result
+ * tensor of the generator pass over those pairs.
+ *
+ * dsee_style_explore: s0, s1 [B][nc][S] (s1 may be s0); src0, src1 [B][n] int32 rows of the batch (values outside [0, B) are
+ * clamped into it); alpha, beta, gamma [n] fp32; noise [B][n][nc][S] or NULL; mask [nc] uint8 -> out [B][n][nc][S].  With
+ * A = s0[src0[b][k]], or out[b][k-1] for k > 0 when recurrent != 0: a row r with mask[r] != 0 becomes
+ * ((alpha[k] * A) + (beta[k] * s1[src1[b][k]])) + gamma[k] (+ noise[b][k]), clamped to [-1, 1] if clamp != 0 -- fp32, one
+ * rounding per operation in that order, nothing contracted; every other row is A, copied.  S % 4 == 0, nc <= 32, buffers
+ * 16-byte aligned, out distinct from s0 and s1. */
+int dsee_style_explore(const float* s0, const float* s1, const int32_t* src0, const int32_t* src1, const float* alpha,
+                       const float* beta, const float* gamma, const float* noise, const uint8_t* mask, float* out, int B, int n,
+                       int nc, int S, int clamp, int recurrent, hipStream_t stream);
+/* dsee_nhwc_to_nchw_tiled: x [pairs][H][W][cs] NHWC (channels 0..2), the generator's output for the pairs
+ * i = pair0 .. pair0 + pairs - 1 of the B * n pairs i = b * n + k -> merge != 0: y [B][3][H][n * W] with
+ * y[b][c][h][k * W + w] (torch.cat(fake_samples, -1)); merge == 0: y [B][n][3][H][W] (torch.stack(fake_samples, 1)).  Only the
+ * elements of those pairs are written, so a pass split into chunks fills y chunk by chunk.  Four-pixel 16-byte stores where the
+ * destination is whole and aligned, single floats at ragged ends. */
+int dsee_nhwc_to_nchw_tiled(const float* x, float* y, int B, int n, int H, int W, int cs, int merge, int pair0, int pairs,
+                            hipStream_t stream);
 /* Test hook (no reference counterpart): fills the LDS of every CU with NaN bit patterns, so that a pipelined kernel
  * launched next shows a read of a not-yet-landed LDS stage as NaN instead of as stale but plausible data.  sink: one float. */
 int dsee_selftest_lds_poison(float* sink, hipStream_t stream);
