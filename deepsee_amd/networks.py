@@ -340,7 +340,7 @@ class SpadeNorm(nn.Module):
             return self._forward_capped(x, labels, training, fm, grad_sink)
         if capped or (self.kind != "spade" and (h * w) % 128 != 0):
             return self._forward_dense(x, labels, style, training, fm, grad_sink)
-        shift = labels.shift_for(h)
+        shift = labels.shift_for(h, w)
         # ---- table path: one fused autograd node per norm; its packed / blended weight set comes from ONE kernel
         P = ops.SeanPack.apply
         am = ops.amax_slot()     # max |packed weights| (and |style table|), written by the producers themselves
@@ -386,13 +386,13 @@ class SpadeNorm(nn.Module):
             add_one = 0.0
         w2a.dsee_amax = am
         return ops.SeanNormTable.apply(x, sh.weight, sh.bias, w2a, None, b2, *self._running(), labels,
-                                       labels.shift_for(fm), training, add_one, grad_sink, ups)
+                                       labels.shift_for(fm, w * fm // h), training, add_one, grad_sink, ups)
 
     def _forward_dense(self, x, labels, style, training, fm, grad_sink=None):
         """General path (style map materialised as 128 gathered channels): resolutions below 16x16, and the
         reference's max_fm_size cap where the upsampled embedding replaces the style map."""
         n, h, w, c = x.shape
-        shift = labels.shift_for(fm)
+        shift = labels.shift_for(fm, w * fm // h)
         cat_ups = 0
         sh = self.mlp_shared._modules["0"]
         capped = fm != h
@@ -567,7 +567,7 @@ class StyleEncoder(nn.Module):
             for nl, s, u in zip(self.norm_layers, [1, 2, 2, 1], [0, 0, 0, 1]):
                 x = nl.apply(self, x, nl.conv(self).weight(training), L.ACT_LRELU, training, stride=s, pad=1, ups=u)
         x = self.final_layer.apply(self, x, self.final_layer.conv(self).weight(training), L.ACT_TANH, training)
-        sm = ops.StylePool.apply(x, labels, labels.shift_for(x.shape[1]))
+        sm = ops.StylePool.apply(x, labels, labels.shift_for(x.shape[1], x.shape[2]))
         if self.scale > 0 and not no_noise:
             # encoder.py:51-70 on the [N,19,S] style matrix (KB-sized parameter-space glue)
             nw = torch.sigmoid(self.noise_weights)[None, :, None]

@@ -221,11 +221,16 @@ class Labels:
         self.n, self.h, self.w = lab_u8.shape
         self.nc = nc
 
-    def shift_for(self, r):
+    def shift_for(self, r, rw=None):
+        """Shift that maps an r x rw feature map (rw None: the same fraction of the width) onto the label map.  Both axes must be
+        the same power-of-two fraction: the label kernels index row h << shift, column w << shift of a [H][W] map."""
         s = 0
         while (self.h >> s) > r:
             s += 1
         assert (self.h >> s) == r, "resolution %d is not a power-of-two fraction of %d" % (r, self.h)
+        if rw is not None:
+            assert (self.w >> s) == rw, \
+                "%d x %d is not the same power-of-two fraction of the %d x %d label map on both axes" % (r, rw, self.h, self.w)
         return s
 
 
@@ -1471,7 +1476,8 @@ class StylePool(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, labels, shift):
         n, hf, wf, c = feat.shape
-        assert hf == labels.h >> shift
+        assert hf == labels.h >> shift and wf == labels.w >> shift, "feature map %d x %d vs labels %d x %d >> %d" % (
+            hf, wf, labels.h, labels.w, shift)
         out = new(n, labels.nc, c)
         ws = scratch(L.lib().dsee_label_segsum_workspace(n, labels.h, labels.w, shift, labels.nc, c), "seg")
         L.call("label_segsum", labels.t, feat, c, 0, out, n, labels.h, labels.w, shift, labels.nc, c,

@@ -687,6 +687,8 @@ int dsee_maxpool2_bwd(const float* dy, const float* x, float* dx, int N, int H, 
 int dsee_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, int Cs, hipStream_t stream);
 int dsee_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, int Cs, hipStream_t stream);
 int dsee_label_to_u8(const float* label, uint8_t* out, long n, hipStream_t stream);
+/* F.interpolate(x, (S, S), mode='bicubic', align_corners=False) + clamp(-1, 1): NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3
+ * channels.  One scale per axis (H / S and W / S): the source may be rectangular, the output is always S x S. */
 int dsee_bicubic_down(const float* x, float* y, int N, int H, int W, int S, int cs_in, int cs_out, hipStream_t stream);
 /* Device input pipeline (replaces the PIL -> float CPU tensors of data/base_dataset.py:87-116,171-201):
  * uint8 HWC images -> NHWC RGB0 fp32 with ToTensor + Normalize((.5,.5,.5),(.5,.5,.5)) and the per-sample horizontal

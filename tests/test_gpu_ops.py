@@ -31,15 +31,30 @@ def gen(seed):
     return torch.Generator().manual_seed(seed)
 
 
-@pytest.mark.parametrize("kind,C,R,N", [("spade", 8, 8, 2), ("sean", 64, 16, 2), ("sean", 128, 8, 3), ("puresean", 32, 8, 2)])
+def _hw(h):
+    """(h, w) of a case: a plain int is the square h x h (the existing cases keep their scalar, and with it their test id)."""
+    return (h, h) if isinstance(h, int) else tuple(h)[:2]
+
+
+def _rect(*vals):
+    """a parametrize entry with a readable id for a case that holds an (h, w[, flag]) tuple"""
+    return pytest.param(*vals, id="-".join("x".join(str(e) for e in v) if isinstance(v, tuple) else str(v) for v in vals))
+
+
+@pytest.mark.parametrize("kind,C,R,N", [("spade", 8, 8, 2), ("sean", 64, 16, 2), ("sean", 128, 8, 3), ("puresean", 32, 8, 2),
+                                        # rectangular, label map 4x the feature map on both axes (32 x 64 / 64 x 32)
+                                        _rect("sean", 64, (8, 16), 2), _rect("spade", 8, (16, 8), 2)])
 def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
     from deepsee_amd import ops, lib as L
+    square = isinstance(R, int)
+    R, Rw = _hw(R)
     g = gen(C * R + N)
-    Lc, S, H = 19, 128, 32
-    label = torch.randint(0, Lc, (N, 1, H, H), generator=g).float()
+    Lc, S = 19, 128
+    H, W = (32, 32) if square else (4 * R, 4 * Rw)
+    label = torch.randint(0, Lc, (N, 1, H, W), generator=g).float()
     seg = O.onehot_labels(label, Lc)
     style = (torch.rand(N, Lc, S, generator=g) * 2 - 1).requires_grad_()
-    x = torch.randn(N, C, R, R, generator=g).requires_grad_()
+    x = torch.randn(N, C, R, Rw, generator=g).requires_grad_()
     spec = {"n.param_free_norm.running_mean": (C,), "n.param_free_norm.running_var": (C,),
             "n.param_free_norm.num_batches_tracked": (), "n.mlp_shared.0.weight": (128, Lc, 3, 3),
             "n.mlp_shared.0.bias": (128,)}
@@ -64,7 +79,7 @@ def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
     # ---- HIP
     dev = "cuda"
     labels = ops.Labels(ops.label_to_u8(label.cuda()), Lc)
-    shift = labels.shift_for(R)
+    shift = labels.shift_for(R, Rw)
     p = {k: v.detach().clone().to(dev).requires_grad_(v.requires_grad) for k, v in st.items() if v.is_floating_point()}
     for k in p:
         if not O.is_buffer(k):
@@ -96,6 +111,10 @@ def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
     h = ops.SpadeNormAct.apply(xs, cat, w2, b2, rm, rv, True, add_one, 0)
     h.backward(nhwc(gy))
     torch.cuda.synchronize()
+    print("%s norm (direct path) C=%d %dx%d: h %.2e dx %.2e, gradients worst %.2e" % (
+        kind, C, R, Rw, rel(nchw(h.detach(), C), y.detach()), rel(nchw(xs.grad, C), x.grad),
+        max([rel(p[k].grad.cpu(), v.grad) for k, v in P.items() if v.requires_grad and v.grad is not None and k in p]
+            + ([rel(sty.grad.cpu(), style.grad)] if want_style else []))))
     assert rel(nchw(h.detach(), C), y.detach()) < TOL
     assert rel(nchw(xs.grad, C), x.grad) < 5 * TOL
     assert rel(rm.cpu(), P["n.param_free_norm.running_mean"]) < TOL
@@ -114,7 +133,11 @@ def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
     # is a shift) and the backward pass reads `out`
     ("sean", 192, 64, 2, 256),
     # the reference's max_fm_size cap (normalization.py:188-190, 275-277): embedding at 32^2 / 16^2, upsampled, style ignored
-    ("puresean", 128, 64, 2, 32), ("sean", 128, 64, 2, 16), ("puresean", 64, 16, 2, 8)])
+    ("puresean", 128, 64, 2, 32), ("sean", 128, 64, 2, 16), ("puresean", 64, 16, 2, 8),
+    # rectangular (h, w, the Winograd domain is expected): 8 x 16 = 128 tiles per image reach it at a height of 32, where the square
+    # 32 x 32 (64 tiles) does not; label map twice the feature map (shift 1)
+    _rect("sean", 64, (32, 64, True), 2, 256), _rect("spade", 64, (64, 32, True), 2, 256),
+    _rect("puresean", 64, (32, 64, True), 2, 256)])
 def test_sean_norm_table_path(kind, C, R, N, max_fm):
     """The production path for R >= 16: style half as per-image one-hot tables (K = 1440 instead of 2304).  From R = 64
     the gamma/beta GEMM, its data gradient and its weight/table gradient run in the Winograd F(4x4,3x3) domain with
@@ -122,12 +145,14 @@ def test_sean_norm_table_path(kind, C, R, N, max_fm):
     masks taken from values within that error of zero flip (a sqrt(fraction) effect on the gradients)."""
     from deepsee_amd import ops, networks as Nw
     from types import SimpleNamespace
+    wino_want = R >= 64 if isinstance(R, int) else R[2]
+    (R, Rw), (H, W) = _hw(R), ((64, 64) if isinstance(R, int) else (2 * R[0], 2 * R[1]))
     g = gen(7 * C + R + N)
-    Lc, S, H = 19, 128, 64
-    label = torch.randint(0, Lc, (N, 1, H, H), generator=g).float()
+    Lc, S = 19, 128
+    label = torch.randint(0, Lc, (N, 1, H, W), generator=g).float()
     seg = O.onehot_labels(label, Lc)
     style = (torch.rand(N, Lc, S, generator=g) * 2 - 1).requires_grad_()
-    x = torch.randn(N, C, R, R, generator=g).requires_grad_()
+    x = torch.randn(N, C, R, Rw, generator=g).requires_grad_()
     mod = Nw.SpadeNorm(kind, C, Lc, S, max_fm)
     st = {"n." + k: O.recipe_tensor("tt_" + kind, k, v.shape, 1.0) for k, v in mod.state_dict().items()}
     orc = O.Oracle(O.make_opt(max_fm_size=max_fm), {"SR": st})
@@ -141,12 +166,15 @@ def test_sean_norm_table_path(kind, C, R, N, max_fm):
     xs = nhwc(x.detach()).requires_grad_()
     sty = style.detach().cuda().requires_grad_()
     capped = kind != "spade" and max_fm < R
-    wino = ops._wino_mod_chunk(N, R, R, C, 2 * C, kind != "spade" and not capped) is not None
-    assert wino == (R >= 64)
+    wino = ops._wino_mod_chunk(N, R, Rw, C, 2 * C, kind != "spade" and not capped) is not None
+    assert wino == wino_want
     h = mod(xs, labels, sty, True)
     h.backward(nhwc(gy))
     torch.cuda.synchronize()
     ft, gt = (1e-4, 5e-3) if wino else (TOL, 2e-4)
+    print("%s norm (table path, winograd %s) C=%d %dx%d: h %.2e dx %.2e, parameter gradients worst %.2e" % (
+        kind, wino, C, R, Rw, rel(nchw(h.detach(), C), y.detach()), rel(nchw(xs.grad, C), x.grad),
+        max(rel(p_.grad.cpu(), P["n." + k].grad) for k, p_ in mod.named_parameters() if P["n." + k].grad is not None)))
     assert rel(nchw(h.detach(), C), y.detach()) < ft
     assert rel(nchw(xs.grad, C), x.grad) < (gt if wino else 5 * TOL)
     assert rel(mod.param_free_norm.running_var.cpu(), P["n.param_free_norm.running_var"]) < TOL
@@ -499,15 +527,19 @@ def test_device_input_pipeline_kernels_bit_exact():
     (3, 64, 128, 33, 4, 2, 2, False),     # 33 -> 17: the two parity classes have 17 and 16 rows
     (2, 64, 128, 64, 4, 2, 2, False),     # even size
     (2, 256, 1, 10, 4, 1, 2, True),       # the discriminator's last layer: 16-output 1x1 GEMM + 16-point gather
-    (3, 256, 1, 35, 4, 1, 2, True)])
+    (3, 256, 1, 35, 4, 1, 2, True),
+    # rectangular: one odd and one even size (the parity classes differ per axis and only one axis is cropped), both orientations
+    _rect(2, 22, 32, (17, 24), 4, 2, 2, True), _rect(2, 22, 32, (24, 17), 4, 2, 2, True),
+    _rect(3, 64, 128, (33, 18), 4, 2, 2, False), _rect(2, 256, 1, (10, 13), 4, 1, 2, True)])
 def test_discriminator_layer_paths(n, cin, cout, h, k, stride, pad, bias):
     """Round 6: the two special forms of the discriminator's convolutions (discriminator.py:78-96) through ops.conv2d against
     F.conv2d autograd in float64 -- the data gradient of the 4 x 4 / stride-2 layers by output parity (one dense 2 x 2
     convolution with 4 Cin output columns + depth-to-space; KernelPlan.dgrad_s2_parity) and the 1-channel last layer as a
     (16 Cout)-output 1x1 GEMM + gather (dsee_thin_gather_k_fwd / _bwd + dsee_thin1x1_bwd).  Output, dx, dw, db <= 2e-5."""
     from deepsee_amd import ops
+    h, wdt = _hw(h)
     g = gen(n * 1000 + cin + h)
-    x = torch.randn(n, cin, h, h, generator=g)
+    x = torch.randn(n, cin, h, wdt, generator=g)
     w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
     b = torch.randn(cout, generator=g) if bias else None
     x6, w6 = x.double().requires_grad_(), w.double().requires_grad_()
@@ -667,13 +699,23 @@ def test_conv_noise_fused_in_output_transform():
     """noise_middle (architecture.py:111-112) fused into the Winograd output transform of conv_0: same values as the
     convolution followed by the stand-alone UpNoise pass on the same Philox stream, same gradients for the input, the
     weights and the noise weight."""
+    _conv_noise_fused(2, 128, 32, 32)
+
+
+def test_conv_noise_fused_in_output_transform_rect():
+    """... on a 16 x 32 map: the Philox stream is indexed in NHWC element order, so a transposed tile index in the output
+    transform (or in the dout transform's noise-weight gradient) gives a pixel another pixel's draw."""
+    _conv_noise_fused(4, 128, 16, 32)
+
+
+def _conv_noise_fused(n, c, h, wdt):
     from deepsee_amd import ops
     g = gen(41)
-    n, c, h = 2, 128, 32
-    x = torch.randn(n, c, h, h, generator=g)
+    assert ops._wino_ok(n, h, wdt, c, c, 3, 1, 1, 0)
+    x = torch.randn(n, c, h, wdt, generator=g)
     w = torch.randn(c, c, 3, 3, generator=g) / (c * 9) ** 0.5
-    b, nw, gy = torch.randn(c, generator=g), torch.randn(c, generator=g), torch.randn(n, c, h, h, generator=g)
-    eps = ops.PhiloxNormal((n, h, h, c), 4242, 1000)
+    b, nw, gy = torch.randn(c, generator=g), torch.randn(c, generator=g), torch.randn(n, c, h, wdt, generator=g)
+    eps = ops.PhiloxNormal((n, h, wdt, c), 4242, 1000)
     outs = []
     for fused in (True, False):
         xd = nhwc(x).requires_grad_()
@@ -686,6 +728,7 @@ def test_conv_noise_fused_in_output_transform():
         y.backward(nhwc(gy))
         outs.append([t.detach().cpu() for t in (y, xd.grad, wd.grad, bd.grad, nd.grad)])
     torch.cuda.synchronize()
+    print("fused noise %dx%d: y, dx, dw, db, dnoise vs the separate pass:" % (h, wdt), ["%.1e" % rel(a, r) for a, r in zip(*outs)])
     for a, r in zip(*outs):
         assert rel(a, r) < 1e-6
     # and the noise really is N(0,1) * nw on top of the convolution
@@ -694,20 +737,21 @@ def test_conv_noise_fused_in_output_transform():
     assert abs(float(z.mean())) < 2e-2 and abs(float(z.std()) - 1.0) < 2e-2
 
 
-@pytest.mark.parametrize("n,c,h", [(2, 128, 32), (8, 256, 16), (8, 512, 32)])
+@pytest.mark.parametrize("n,c,h", [(2, 128, 32), (8, 256, 16), (8, 512, 32), _rect(4, 128, (16, 32))])
 def test_batchnorm_statistics_from_the_producers(n, c, h):
     """The BatchNorm statistics of a SPADE/SEAN norm whose input comes from UpNoise (norm_0) or from a Winograd convolution
     with fused noise (conv_0 -> norm_1) are written by those kernels (rows of (count, mean, M2) per workgroup, folded by
     dsee_norm_stats_finalize_parts; sync_batchnorm/batchnorm.py:65-68).  Against float64 statistics of the produced tensor
     and against the separate statistics pass: mean / invstd <= 2e-6, identical running-statistics update."""
     from deepsee_amd import ops
+    h, wdt = _hw(h)
     g = gen(n * c + h)
-    x = (torch.randn(n, c, h, h, generator=g) * 2 + torch.randn(1, c, 1, 1, generator=g) * 3)
+    x = (torch.randn(n, c, h, wdt, generator=g) * 2 + torch.randn(1, c, 1, 1, generator=g) * 3)
     nw = torch.randn(c, generator=g).cuda()
     w = (torch.randn(c, c, 3, 3, generator=g) / (c * 9) ** 0.5).cuda()
     b = torch.randn(c, generator=g).cuda()
-    eps1 = ops.PhiloxNormal((n, 2 * h, 2 * h, c), 99, 5000)
-    eps2 = ops.PhiloxNormal((n, h, h, c), 99, 777)
+    eps1 = ops.PhiloxNormal((n, 2 * h, 2 * wdt, c), 99, 5000)
+    eps2 = ops.PhiloxNormal((n, h, wdt, c), 99, 777)
     producers = {"up_noise": lambda st: ops.UpNoise.apply(nhwc(x), nw, eps1, 1, st),
                  "wino_output": lambda st: ops.conv2d(nhwc(x), w, b, noise=(nw, eps2), stats=st)}
     for name, make in producers.items():
@@ -724,6 +768,8 @@ def test_batchnorm_statistics_from_the_producers(n, c, h):
         mu, var = y64.mean(0), y64.var(0, unbiased=False)
         inv = 1.0 / torch.sqrt(var + ops.BN_EPS)
         for got in ((mean_a, inv_a), (mean_b, inv_b)):
+            print("statistics from %s %dx%d: mean %.1e invstd %.1e" % (name, h, wdt, float((got[0].double() - mu).abs().max()
+                  / mu.abs().max()), float(((got[1].double() - inv) / inv).abs().max())))
             assert float((got[0].double() - mu).abs().max() / mu.abs().max()) < 2e-6, name
             assert float(((got[1].double() - inv) / inv).abs().max()) < 2e-6, name
         assert float((rm_a - rm_b).abs().max()) < 1e-6 and float(((rv_a - rv_b) / rv_b).abs().max()) < 1e-6, name
