@@ -1,0 +1,162 @@
+// Load-time geometry of the input pipeline on the device (deepsee_amd/resample.py builds the tables, deepsee_amd/data.py calls):
+//   dsee_resample_u8   Pillow's 8-bit separable resize (Image.resize with BICUBIC / BILINEAR / NEAREST on 'RGB' and 'L' images),
+//                      bit for bit, with the centre crop as a source box and the random crop as an output window
+//   dsee_interp_down   F.interpolate(hr, (S, S), mode = bilinear | nearest | area) + clamp(-1, 1)  (data/preprocessor.py:29-33)
+#include "dsee_common.h"
+
+namespace {
+
+inline int rgrid(long n) { return (int)min(8192L, (n + 255) / 256); }
+
+// One axis of Pillow's ImagingResample for 8-bit pixels: acc = 1 << 21; acc += pixel * k over the taps; clip8(acc >> 22).
+// Integer arithmetic only; `>>` of a negative int is an arithmetic shift on this target, as in Pillow's clip8 lookup.
+constexpr int RS_BITS = 22;
+__device__ __forceinline__ uint8_t rs_clip8(int acc) {
+  const int v = acc >> RS_BITS;
+  return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+// A table row is (first source index, tap count, k[0 .. kmax - 1]).  `rows` holds (first source row, row count) per sample: the
+// source rows the sample's output window reads through its vertical taps.  tmp[n][r][xo][c] = horizontal pass of source row
+// rows[2n] + r, r < rows[2n + 1].  Indices are clamped to the source box: a malformed table cannot read outside it.
+template <int C>
+__global__ __launch_bounds__(256) void resample_h_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ tmp, int N,
+                                                         long n_stride, int row_stride, int box_w, int box_h, int Wo,
+                                                         int tmp_rows, const int32_t* __restrict__ xtab, int kx,
+                                                         const int32_t* __restrict__ rows) {
+  const long total = (long)N * tmp_rows * Wo;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % Wo);
+    const long t = i / Wo;
+    const int r = (int)(t % tmp_rows), n = (int)(t / tmp_rows);
+    const int sr = rows[2 * n] + r;
+    if (r >= rows[2 * n + 1] || sr < 0 || sr >= box_h) continue;
+    const int32_t* tab = xtab + ((long)n * Wo + xo) * (2 + kx);
+    const int first = max(tab[0], 0);
+    const int cnt = min(min(tab[1], kx), box_w - first);
+    const uint8_t* p = src + n * n_stride + (long)sr * row_stride + (long)first * C;
+    int acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 1 << (RS_BITS - 1);
+    for (int k = 0; k < cnt; ++k) {
+      const int kk = tab[2 + k];
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] += (int)p[k * C + c] * kk;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) tmp[i * C + c] = rs_clip8(acc[c]);
+  }
+}
+
+// dst[n][yo][xo][c] = vertical pass over tmp; the `first` of a ytab row counts from the sample's first tmp row
+template <int C>
+__global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restrict__ tmp, uint8_t* __restrict__ dst, int N, int Wo,
+                                                         int Ho, int tmp_rows, const int32_t* __restrict__ ytab, int ky,
+                                                         const int32_t* __restrict__ rows) {
+  const long total = (long)N * Ho * Wo;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % Wo);
+    const long t = i / Wo;
+    const int yo = (int)(t % Ho), n = (int)(t / Ho);
+    const int32_t* tab = ytab + ((long)n * Ho + yo) * (2 + ky);
+    const int first = max(tab[0], 0);
+    const int cnt = min(min(tab[1], ky), min(rows[2 * n + 1], tmp_rows) - first);
+    const uint8_t* p = tmp + (((long)n * tmp_rows + first) * Wo + xo) * C;
+    int acc[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] = 1 << (RS_BITS - 1);
+    for (int k = 0; k < cnt; ++k) {
+      const int kk = tab[2 + k];
+#pragma unroll
+      for (int c = 0; c < C; ++c) acc[c] += (int)p[(long)k * Wo * C + c] * kk;
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) dst[i * C + c] = rs_clip8(acc[c]);
+  }
+}
+
+enum { INTERP_BILINEAR = 0, INTERP_NEAREST = 1, INTERP_AREA = 2 };
+
+// source index and weight of the upper neighbour of ATen's upsample_bilinear2d (align_corners = False)
+__device__ __forceinline__ void bilinear_tap(float scale, int dst, int in, int& i0, int& i1, float& l1) {
+  const float s = fmaxf(scale * (dst + 0.5f) - 0.5f, 0.f);
+  i0 = min((int)s, in - 1);
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
+}
+
+// NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3 channels (the rest of cs_out zero); sh = (float)H / S, sw = (float)W / S from the
+// host, so that the nearest index is the one ATen computes: min((int)floorf(dst * scale), in - 1)
+__global__ __launch_bounds__(256) void interp_down_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W,
+                                                          int S, int cs_in, int cs_out, int mode, float sh, float sw) {
+  const long total = (long)N * S * S;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ow = (int)(i % S);
+    const long t = i / S;
+    const int oh = (int)(t % S), n = (int)(t / S);
+    const float* img = x + (size_t)n * H * W * cs_in;
+    float v[3] = {0.f, 0.f, 0.f};
+    if (mode == INTERP_NEAREST) {
+      const int iy = min((int)floorf(oh * sh), H - 1), ix = min((int)floorf(ow * sw), W - 1);
+      for (int c = 0; c < 3; ++c) v[c] = img[((size_t)iy * W + ix) * cs_in + c];
+    } else if (mode == INTERP_BILINEAR) {
+      int y0, y1, x0, x1;
+      float ly, lx;
+      bilinear_tap(sh, oh, H, y0, y1, ly);
+      bilinear_tap(sw, ow, W, x0, x1, lx);
+      for (int c = 0; c < 3; ++c) {
+        const float a = img[((size_t)y0 * W + x0) * cs_in + c], b = img[((size_t)y0 * W + x1) * cs_in + c];
+        const float d = img[((size_t)y1 * W + x0) * cs_in + c], e = img[((size_t)y1 * W + x1) * cs_in + c];
+        v[c] = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e);
+      }
+    } else {  // adaptive average: rows floor(i in / out) ... ceil((i + 1) in / out)
+      const int ya = (int)(((long)oh * H) / S), yb = (int)((((long)oh + 1) * H + S - 1) / S);
+      const int xa = (int)(((long)ow * W) / S), xb = (int)((((long)ow + 1) * W + S - 1) / S);
+      for (int yy = ya; yy < yb; ++yy) {
+        float row[3] = {0.f, 0.f, 0.f};
+        for (int xx = xa; xx < xb; ++xx)
+          for (int c = 0; c < 3; ++c) row[c] += img[((size_t)yy * W + xx) * cs_in + c];
+        for (int c = 0; c < 3; ++c) v[c] += row[c];
+      }
+      const float inv = (float)((yb - ya) * (xb - xa));
+      for (int c = 0; c < 3; ++c) v[c] /= inv;
+    }
+    float* o = y + (size_t)i * cs_out;
+    for (int c = 0; c < cs_out; ++c) o[c] = c < 3 ? fminf(fmaxf(v[c], -1.f), 1.f) : 0.f;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dsee_resample_u8(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int N, int C, long src_off, long src_n_stride,
+                     int src_row_stride, int box_w, int box_h, int Wo, int Ho, int tmp_rows, const int32_t* xtab, int kx,
+                     const int32_t* ytab, int ky, const int32_t* rows, hipStream_t st) {
+  DSEE_CHECK_ARG(src && tmp && dst && xtab && ytab && rows && (C == 1 || C == 3));
+  DSEE_CHECK_ARG(N > 0 && box_w > 0 && box_h > 0 && Wo > 0 && Ho > 0 && tmp_rows > 0 && tmp_rows <= box_h && kx > 0 && ky > 0);
+  DSEE_CHECK_ARG(src_off >= 0 && src_row_stride >= box_w * C && src_n_stride >= (long)src_row_stride * (box_h - 1) + box_w * C);
+  const long nh = (long)N * tmp_rows * Wo, nv = (long)N * Ho * Wo;
+  if (C == 3) {
+    resample_h_kernel<3><<<rgrid(nh), 256, 0, st>>>(src + src_off, tmp, N, src_n_stride, src_row_stride, box_w, box_h, Wo,
+                                                    tmp_rows, xtab, kx, rows);
+    resample_v_kernel<3><<<rgrid(nv), 256, 0, st>>>(tmp, dst, N, Wo, Ho, tmp_rows, ytab, ky, rows);
+  } else {
+    resample_h_kernel<1><<<rgrid(nh), 256, 0, st>>>(src + src_off, tmp, N, src_n_stride, src_row_stride, box_w, box_h, Wo,
+                                                    tmp_rows, xtab, kx, rows);
+    resample_v_kernel<1><<<rgrid(nv), 256, 0, st>>>(tmp, dst, N, Wo, Ho, tmp_rows, ytab, ky, rows);
+  }
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_interp_down(const float* x, float* y, int N, int H, int W, int S, int cs_in, int cs_out, int mode, hipStream_t st) {
+  DSEE_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && S > 0 && cs_in >= 3 && cs_out >= 3);
+  DSEE_CHECK_ARG(mode == INTERP_BILINEAR || mode == INTERP_NEAREST || mode == INTERP_AREA);
+  interp_down_kernel<<<rgrid((long)N * S * S), 256, 0, st>>>(x, y, N, H, W, S, cs_in, cs_out, mode, (float)H / (float)S,
+                                                             (float)W / (float)S);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+}  // extern "C"

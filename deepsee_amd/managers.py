@@ -29,10 +29,10 @@ class BaseManager:
 
     def preprocess(self, data, from_dataloader=False):
         """base_manager.py:28-66 + data/preprocessor.py: label -> integer map (kept as uint8 instead of a one-hot
-        tensor), HR -> LR bicubic + clamp, everything NHWC on the device."""
+        tensor), HR -> LR by opt.downsampling_method + clamp, everything NHWC on the device."""
         if isinstance(data.get("input_semantics"), ops.Labels):
             return data        # already native: a batch of deepsee_amd.data.DeviceLoader (SURVEY 8 f3)
-        if from_dataloader and data["image"].dtype == torch.uint8:
+        if from_dataloader and ("image_raw" in data or data["image"].dtype == torch.uint8):
             from .data import device_preprocess      # uint8 wire format: [N,H,W] labels, [N,H,W,3] images
             return device_preprocess(self.opt, data)
         out = dict(data)
@@ -45,7 +45,7 @@ class BaseManager:
         image = ops.to_nhwc(out["image"])
         res = {
             "input_semantics": ops.Labels(ops.label_to_u8(out["label"]), opt.label_nc),
-            "image_lr": ops.bicubic_down(image, opt.start_size),
+            "image_lr": ops.lr_image(opt, image),
             "image_hr": image,
         }
         if opt.guiding_style_image:

@@ -202,6 +202,52 @@ def bicubic_down(img_nhwc, size):
     return y
 
 
+INTERP_MODES = {"bilinear": 0, "nearest": 1, "area": 2}
+
+
+def interp_down(img_nhwc, size, mode):
+    """F.interpolate(hr, (size, size), mode) + clamp(-1, 1) for mode = bilinear | nearest | area (data/preprocessor.py:29-33) of a
+    native image [N,H,W,cs], H and W independent -> [N,size,size,4]."""
+    if mode not in INTERP_MODES:
+        raise ValueError("interp_down: mode must be one of %s, got %r" % (", ".join(INTERP_MODES), mode))
+    n, h, w, cs = img_nhwc.shape
+    y = new(n, size, size, 4)
+    L.call("interp_down", img_nhwc.contiguous(), y, n, h, w, size, cs, 4, INTERP_MODES[mode])
+    y.dsee_layout = "nhwc"
+    return y
+
+
+def lr_image(opt, hr_nhwc):
+    """The LR input of the generator: opt.downsampling_method selects the F.interpolate mode (preprocessor.py:29-30).  bicubic is
+    the kernel it has always been."""
+    mode = getattr(opt, "downsampling_method", "bicubic")
+    if mode == "bicubic":
+        return bicubic_down(hr_nhwc, opt.start_size)
+    if mode not in INTERP_MODES:       # the reference's help text offers 'linear', which F.interpolate rejects for 4-D input
+        raise ValueError("downsampling_method must be one of bicubic, %s, got %r" % (", ".join(INTERP_MODES), mode))
+    return interp_down(hr_nhwc, opt.start_size, mode)
+
+
+def resample_u8(src, tables, out_wh, box=None):
+    """dsee_resample_u8: uint8 device batch [N,Hs,Ws,C] (or [N,Hs,Ws]) through the tables of resample.batch_tables (already on
+    the device: int32 tensors 'xtab', 'ytab', 'rows' + the int 'tmp_rows') -> uint8 [N,Ho,Wo,C] (resp. [N,Ho,Wo]).  box =
+    (x, y, w, h) of the source the tables index; default: the whole image."""
+    src = src.contiguous()
+    c = src.shape[3] if src.dim() == 4 else 1
+    n, hs, ws = src.shape[:3]
+    x0, y0, bw, bh = box if box is not None else (0, 0, ws, hs)
+    assert 0 <= x0 and 0 <= y0 and x0 + bw <= ws and y0 + bh <= hs and src.dtype == torch.uint8, (box, tuple(src.shape))
+    wo, ho = out_wh
+    xtab, ytab, rows, tmp_rows = tables["xtab"], tables["ytab"], tables["rows"], tables["tmp_rows"]
+    assert tuple(xtab.shape[:2]) == (n, wo) and tuple(ytab.shape[:2]) == (n, ho) and tuple(rows.shape) == (n, 2)
+    assert xtab.dtype == ytab.dtype == rows.dtype == torch.int32 and 0 < tmp_rows <= bh
+    tmp = scratch(n * tmp_rows * wo * c, "resample").view(torch.uint8)
+    dst = torch.empty((n, ho, wo, c) if src.dim() == 4 else (n, ho, wo), dtype=torch.uint8, device="cuda")
+    L.call("resample_u8", src, tmp, dst, n, c, (y0 * ws + x0) * c, hs * ws * c, ws * c, bw, bh, wo, ho, tmp_rows,
+           xtab, xtab.shape[2] - 2, ytab, ytab.shape[2] - 2, rows)
+    return dst
+
+
 def bicubic_up(img_nhwc, h, w, clamp=True):
     """F.interpolate(x, (h, w), mode='bicubic')[.clamp(-1, 1)] of a square native image [N,S,S,cs] -> [N,h,w,4] (the 'baseline'
     every SR table is compared against, sr_model.py:109-115)."""

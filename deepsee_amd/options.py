@@ -25,6 +25,7 @@ DEFAULTS = dict(
     sync_bn=False,           # data-parallel: BatchNorm statistics over the global batch; default sync-free
     sync_bn_clamp=True,      # ... with the reference DP branch's clamp(var, eps) (batchnorm.py:145) instead of var + eps
     preprocess_mode="resize_and_crop", no_flip=False,
+    center_crop_size=None,   # options/base_options.py:64 (178 for CelebA): the center_crop* modes of data.RawFolderDataset
     hip_graphs=True,         # capture the G and the D step as hipGraphs (one per encoder-branch variant and batch shape) and
                              # replay them: 0.5 ms instead of ~60 ms of Python launch enqueue per step
     max_graph_shapes=4,      # ... for at most this many distinct batch shapes (least recently used evicted)

@@ -697,6 +697,24 @@ int dsee_image_u8_to_nhwc(const uint8_t* img, const uint8_t* flip, float* out, i
                           hipStream_t stream);
 int dsee_label_u8_prepare(const uint8_t* lab, const uint8_t* flip, uint8_t* out, int N, int H, int W, int unknown_to,
                           hipStream_t stream);
+/* Load-time geometry on the device: the Image.resize / CenterCrop / crop calls of data/base_dataset.py:171-201,208-245
+ * (transforms.Resize, __scale_width, __scale_shortside, __resize, __crop) as ONE separable resampling of a uint8 batch
+ * [N][Hs][Ws][C], C = 3 or 1, that equals Pillow's 8-bit result bit for bit.  Integer arithmetic only, driven by tables built
+ * on the host (deepsee_amd/resample.py): a table row is (first source index, tap count, kmax int32 coefficients scaled by 2^22);
+ * xtab holds N * Wo rows of 2 + kx values, ytab N * Ho rows of 2 + ky values -- only the rows of the output window (the random
+ * crop), per sample.  The source box (the centre crop) is src_off bytes into src, box_w x box_h pixels, with strides in bytes.
+ * rows[2n], rows[2n + 1] = first source row (inside the box) and number of source rows that sample n's window reads; the
+ * horizontal pass runs over those alone, into the uint8 intermediate tmp [N][tmp_rows][Wo][C] (tmp_rows >= every row count),
+ * and the `first` of a ytab row counts from rows[2n].  Each pass: acc = 2^21 + sum(pixel * k), stored as clip(acc >> 22, 0, 255).
+ * A nearest-neighbour or unchanged axis is a one-tap table with k = 2^22. */
+int dsee_resample_u8(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int N, int C, long src_off, long src_n_stride,
+                     int src_row_stride, int box_w, int box_h, int Wo, int Ho, int tmp_rows, const int32_t* xtab, int kx,
+                     const int32_t* ytab, int ky, const int32_t* rows, hipStream_t stream);
+/* F.interpolate(x, (S, S), mode) + clamp(-1, 1) of data/preprocessor.py:29-33 for the modes other than bicubic: mode 0 = bilinear
+ * (align_corners=False, no antialias), 1 = nearest (floorf(dst * (float)in / out) capped at in - 1), 2 = area (adaptive average
+ * over floor(i in / out) ... ceil((i + 1) in / out)).  NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3 channels, like
+ * dsee_bicubic_down: the source may be rectangular. */
+int dsee_interp_down(const float* x, float* y, int N, int H, int W, int S, int cs_in, int cs_out, int mode, hipStream_t stream);
 /* cat([input_semantics, image], dim=1) of sr_model.py:655-668 in NHWC, and the image part of its gradient */
 int dsee_build_d_input(const uint8_t* lab, const float* img, float* out, long pixels, int L, int Cs, int img_cs,
                        hipStream_t stream);
