@@ -9,6 +9,7 @@
 //    divides by H*W not by region area), also the backward of label_gather.
 //  * nearest resize of the label map is index math: src = dst << shift  (F.interpolate 'nearest', SURVEY B-3).
 #include "dsee_common.h"
+#include "dsee_rng.h"
 
 namespace {
 
@@ -354,6 +355,184 @@ __global__ void segsum_finalize_kernel(const float* __restrict__ part, int chunk
   table[i] = v * scale;
 }
 
+// ---- one-hot x noise conv3x3: the first layer of FullStyleEncoder under opt.random_style_matrix (encoder.py:116-120).  Its input
+// randn(N, L, H, W) * one-hot(seg) has ONE non-zero channel per pixel -- the pixel's own class, holding the scalar eps(n, y, x)
+// -- so the dense L -> Co convolution is the gather-sum of onehot_conv3x3 with one extra factor per tap:
+//   out[n,y,x,:] = bias + sum_tap table[tap][lab(q)][:] * eps(q),   q = (n, y + ky - 1, x + kx - 1), zero padding.
+// eps comes from a tensor field[N][H][W], or (field == NULL) from the Philox stream (seed, offset): pixel p = (n*H + y)*W + x is
+// component p & 3 of philox_normal4(seed, offset + (p >> 2)), i.e. what dsee_rng_fill writes for an [N,H,W,1] normal tensor.
+constexpr int NZ_TH = 16, NZ_TW = 32;                    // output tile (rows x columns) of one block pass
+constexpr int NZ_HW = NZ_TW + 2, NZ_HALO = (NZ_TH + 2) * NZ_HW;
+constexpr int NZ_SLOTS = (NZ_HW + 3) / 4 + 1;            // Philox counters a halo row can touch, whatever its alignment
+
+// Labels (-1: outside the image or >= L: contributes nothing) and eps of the tile at (n, y0, x0) with its one-pixel halo.
+// Every Philox counter the tile touches is evaluated once, by one thread.  Ends with a barrier.
+__device__ __forceinline__ void noise_tile_stage(const uint8_t* __restrict__ lab, const float* __restrict__ field, uint64_t seed,
+                                                 uint64_t offset, int n, int y0, int x0, int H, int W, int L, int* lab_s,
+                                                 float* eps_s) {
+  for (int i = threadIdx.x; i < NZ_HALO; i += blockDim.x) {
+    const int r = i / NZ_HW, c = i - r * NZ_HW;
+    const int y = y0 - 1 + r, x = x0 - 1 + c;
+    const bool in = y >= 0 && y < H && x >= 0 && x < W;
+    const size_t p = ((size_t)n * H + (in ? y : 0)) * W + (in ? x : 0);
+    const int v = in ? (int)lab[p] : -1;
+    lab_s[i] = v < L ? v : -1;
+    if (field) eps_s[i] = in ? field[p] : 0.f;
+    else if (!in) eps_s[i] = 0.f;       // (the pixels inside the image are written below, each by exactly one thread)
+  }
+  if (!field) {
+    for (int i = threadIdx.x; i < (NZ_TH + 2) * NZ_SLOTS; i += blockDim.x) {
+      const int r = i / NZ_SLOTS, k = i - r * NZ_SLOTS;
+      const int y = y0 - 1 + r;
+      const int xa = max(x0 - 1, 0), xb = min(x0 + NZ_TW, W - 1);
+      if (y < 0 || y >= H || xa > xb) continue;
+      const uint64_t pa = ((uint64_t)n * H + y) * W + xa, pb = pa + (uint64_t)(xb - xa);
+      const uint64_t ctr = (pa >> 2) + (uint64_t)k;
+      if (ctr > (pb >> 2)) continue;
+      const f32x4 v = philox_normal4(seed, offset + ctr);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint64_t p = ctr * 4 + j;
+        if (p >= pa && p <= pb) eps_s[r * NZ_HW + (xa - (x0 - 1)) + (int)(p - pa)] = v[j];
+      }
+    }
+  }
+  __syncthreads();
+}
+
+// table [9][L][Co] in LDS next to the staged tile; 256 threads, Co / 4 threads per pixel (256 % (Co / 4) == 0), float4 stores
+__global__ __launch_bounds__(256) void onehot_noise_fwd_kernel(const uint8_t* __restrict__ lab, const float* __restrict__ field,
+                                                               uint64_t seed, uint64_t offset,
+                                                               const uint64_t* __restrict__ epoch,
+                                                               const float* __restrict__ wt, const float* __restrict__ bias,
+                                                               float* __restrict__ out, int N, int H, int W, int L, int Co,
+                                                               int tiles_x, int tiles_y) {
+  extern __shared__ __attribute__((aligned(16))) float nz_smem[];
+  float* const tab = nz_smem;                            // [9][L][Co]
+  float* const eps_s = tab + 9 * L * Co;                 // [NZ_HALO]
+  int* const lab_s = reinterpret_cast<int*>(eps_s + NZ_HALO);
+  if (epoch) offset += *epoch;
+  for (int i = threadIdx.x; i < 9 * L * Co / 4; i += 256)
+    reinterpret_cast<f32x4*>(tab)[i] = reinterpret_cast<const f32x4*>(wt)[i];
+  const unsigned b = blockIdx.x, tx_ = b % (unsigned)tiles_x, t_ = b / (unsigned)tiles_x;
+  const int ty_ = (int)(t_ % (unsigned)tiles_y), n = (int)(t_ / (unsigned)tiles_y);
+  const int y0 = ty_ * NZ_TH, x0 = (int)tx_ * NZ_TW;
+  noise_tile_stage(lab, field, seed, offset, n, y0, x0, H, W, L, lab_s, eps_s);   // (its barrier covers the table too)
+  const int tpp = Co / 4, ppb = 256 / tpp;
+  const int q = threadIdx.x % tpp, s = threadIdx.x / tpp;
+  const f32x4 bv = bias ? *reinterpret_cast<const f32x4*>(bias + q * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
+  const float* const tq = tab + q * 4;
+  for (int pix = s; pix < NZ_TH * NZ_TW; pix += ppb) {
+    const int ty = pix / NZ_TW, tx = pix % NZ_TW;
+    const int y = y0 + ty, x = x0 + tx;
+    if (y >= H || x >= W) continue;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int h = (ty + tap / 3) * NZ_HW + tx + tap % 3;
+      const int r = lab_s[h];
+      if (r >= 0) acc += *reinterpret_cast<const f32x4*>(tq + (tap * L + r) * Co) * eps_s[h];
+    }
+    acc += bv;       // (last: the bias then enters one rounding, not the nine of the tap sum)
+    *reinterpret_cast<f32x4*>(out + (((size_t)n * H + y) * W + x) * Co + q * 4) = acc;
+  }
+}
+
+// Weight gradient: dw[co][c][tap] = sum_p [lab(p + tap) = c] eps(p + tap) dout[p][co] over the output pixels p.  Thread = (tap,
+// co); its L class accumulators are a private column of LDS, accs[c][thread], indexed by the label: one read-add-write per pixel
+// and no conflict (a wave's threads hit consecutive words) -- the compare-select chain over registers of onehot_conv_wgrad_kernel
+// costs 3 L instructions per pixel.  A block walks the tiles b, b + gridDim.x, ... in that
+// order and writes ONE partial [9 L + 1][Co]: fixed summation order, no atomics.  The centre tap's threads also sum dout for the
+// bias.
+__global__ __launch_bounds__(1024) void onehot_noise_wgrad_kernel(const uint8_t* __restrict__ lab,
+                                                                  const float* __restrict__ field, uint64_t seed,
+                                                                  uint64_t offset, const uint64_t* __restrict__ epoch,
+                                                                  const float* __restrict__ dout, int N, int H, int W, int L,
+                                                                  int Co, int tiles_x, int tiles_y, int tiles,
+                                                                  float* __restrict__ part) {
+  __shared__ float eps_s[NZ_HALO];
+  __shared__ int lab_s[NZ_HALO];
+  extern __shared__ float nz_accs[];             // [L][blockDim.x]
+  if (epoch) offset += *epoch;
+  const int T = blockDim.x;
+  const int tap = threadIdx.x / Co, co = threadIdx.x - tap * Co;
+  const bool live = tap < 9;
+  const int hoff = (tap / 3) * NZ_HW + tap % 3;
+  float* const mine = nz_accs + threadIdx.x;
+  for (int k = 0; k < L; ++k) mine[k * T] = 0.f;
+  float accb = 0.f;
+  for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const unsigned tu = (unsigned)t, tx_ = tu % (unsigned)tiles_x, t_ = tu / (unsigned)tiles_x;
+    const int ty_ = (int)(t_ % (unsigned)tiles_y), n = (int)(t_ / (unsigned)tiles_y);
+    const int y0 = ty_ * NZ_TH, x0 = (int)tx_ * NZ_TW;
+    __syncthreads();            // (the previous tile's readers are done)
+    noise_tile_stage(lab, field, seed, offset, n, y0, x0, H, W, L, lab_s, eps_s);
+    if (!live) continue;
+    const int th = min(NZ_TH, H - y0), tw = min(NZ_TW, W - x0);
+    for (int ty = 0; ty < th; ++ty) {
+      const float* const drow = dout + (((size_t)n * H + y0 + ty) * W + x0) * Co + co;
+      const int hrow = ty * NZ_HW + hoff;
+      if (tw == NZ_TW) {
+        // a full row: its 32 loads are in flight together (one at a time, the loop ran at a load latency per pixel: 370 us for
+        // 8 x 256^2 x 32); the sums below keep the pixel order of the general loop
+        float g[NZ_TW];
+#pragma unroll
+        for (int tx = 0; tx < NZ_TW; ++tx) g[tx] = drow[(size_t)tx * Co];
+#pragma unroll
+        for (int tx = 0; tx < NZ_TW; ++tx) {
+          const int r = lab_s[hrow + tx];
+          const float e = eps_s[hrow + tx];
+          accb += g[tx];
+          if (r >= 0) mine[r * T] += g[tx] * e;
+        }
+      } else {
+        for (int tx = 0; tx < tw; ++tx) {
+          const float g = drow[(size_t)tx * Co];
+          const int r = lab_s[hrow + tx];
+          const float e = eps_s[hrow + tx];
+          accb += g;
+          if (r >= 0) mine[r * T] += g * e;
+        }
+      }
+    }
+  }
+  if (!live) return;
+  float* const o = part + (size_t)blockIdx.x * (9 * L + 1) * Co;
+  for (int k = 0; k < L; ++k) o[(tap * L + k) * Co + co] = mine[k * T];
+  if (tap == 4) o[9 * L * Co + co] = accb;
+}
+
+// dw [Co][L][3][3] (+ db [Co]) = the partials summed in index order, four interleaved chains joined in a fixed order
+__global__ void onehot_noise_wgrad_finalize_kernel(const float* __restrict__ part, int nparts, int L, int Co,
+                                                   float* __restrict__ dw, float* __restrict__ db) {
+  const int rows = 9 * L + 1;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * Co) return;
+  const int c = i % Co, row = i / Co;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+  int p = 0;
+  for (; p + 4 <= nparts; p += 4) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] += part[(size_t)(p + j) * rows * Co + i];
+  }
+  for (int j = 0; p < nparts; ++p, ++j) v[j] += part[(size_t)p * rows * Co + i];
+  const float s = (v[0] + v[1]) + (v[2] + v[3]);
+  if (row == 9 * L) {
+    if (db) db[c] = s;
+  } else {
+    const int tap = row / L, r = row % L;
+    dw[((size_t)c * L + r) * 9 + tap] = s;
+  }
+}
+
+int noise_tiles(int N, int H, int W, int* tiles_x, int* tiles_y) {
+  *tiles_x = (W + NZ_TW - 1) / NZ_TW;
+  *tiles_y = (H + NZ_TH - 1) / NZ_TH;
+  return N * *tiles_x * *tiles_y;
+}
+
+constexpr int NZ_MAX_PARTS = 512;
+
 int seg_chunks(int N, int P, int* chunk_px) {
   int want = 1024 / (N > 0 ? N : 1);
   if (want < 1) want = 1;
@@ -452,6 +631,51 @@ int dsee_onehot_conv3x3_wgrad(const uint8_t* lab, const float* dact, int dact_ld
   DSEE_LAUNCH_CHECK();
   onehot_wgrad_finalize_kernel<<<dsee_cdiv((long)(9 * L + 1) * 128, 256), 256, 0, st>>>(workspace, parts, L, dw_oihw,
                                                                                         dbias);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_onehot_noise_conv3x3_fwd(const uint8_t* lab, const float* field, uint64_t seed, uint64_t offset, int use_epoch,
+                                  const float* table, const float* bias, float* out, int N, int H, int W, int L, int Co,
+                                  hipStream_t st) {
+  DSEE_CHECK_ARG(lab && table && out && N > 0 && H > 0 && W > 0 && L > 0 && L <= 32);
+  DSEE_CHECK_ARG(Co > 0 && Co % 4 == 0 && 256 % (Co / 4) == 0);
+  DSEE_CHECK_ARG((long)N * H * W < (1L << 31));
+  const size_t lds = (size_t)9 * L * Co * sizeof(float) + (size_t)NZ_HALO * (sizeof(float) + sizeof(int));
+  DSEE_CHECK_ARG(lds <= 64 * 1024);      // (the whole tap table sits in LDS: Co <= 48 at 32 classes, <= 80 at 19)
+  int tx, ty;
+  const int tiles = noise_tiles(N, H, W, &tx, &ty);
+  onehot_noise_fwd_kernel<<<tiles, 256, lds, st>>>(lab, field, seed, offset, (use_epoch && !field) ? dsee_rng_epoch() : nullptr,
+                                                   table, bias, out, N, H, W, L, Co, tx, ty);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+size_t dsee_onehot_noise_conv3x3_wgrad_workspace(int N, int H, int W, int L, int Co) {
+  if (N <= 0 || H <= 0 || W <= 0 || L <= 0 || Co <= 0) return 0;
+  int tx, ty;
+  const int tiles = noise_tiles(N, H, W, &tx, &ty);
+  return (size_t)min(tiles, NZ_MAX_PARTS) * (9 * L + 1) * Co * sizeof(float);
+}
+
+int dsee_onehot_noise_conv3x3_wgrad(const uint8_t* lab, const float* field, uint64_t seed, uint64_t offset, int use_epoch,
+                                    const float* dout, int N, int H, int W, int L, int Co, float* dw_oihw, float* dbias,
+                                    float* workspace, hipStream_t st) {
+  DSEE_CHECK_ARG(lab && dout && dw_oihw && workspace && N > 0 && H > 0 && W > 0 && L > 0 && L <= 32);
+  DSEE_CHECK_ARG(Co > 0 && Co % 4 == 0 && 9 * Co <= 1024);
+  DSEE_CHECK_ARG((long)N * H * W < (1L << 31));
+  int tx, ty;
+  const int tiles = noise_tiles(N, H, W, &tx, &ty);
+  const int parts = min(tiles, NZ_MAX_PARTS);
+  const int threads = max(256, (9 * Co + 63) / 64 * 64);
+  const uint64_t* const ep = (use_epoch && !field) ? dsee_rng_epoch() : nullptr;
+  const size_t lds = (size_t)L * threads * sizeof(float);
+  DSEE_CHECK_ARG(lds + (size_t)NZ_HALO * (sizeof(float) + sizeof(int)) <= 64 * 1024);   // (L accumulators per (tap, co) in LDS)
+  onehot_noise_wgrad_kernel<<<parts, threads, lds, st>>>(lab, field, seed, offset, ep, dout, N, H, W, L, Co, tx, ty, tiles,
+                                                         workspace);
+  DSEE_LAUNCH_CHECK();
+  onehot_noise_wgrad_finalize_kernel<<<dsee_cdiv((long)(9 * L + 1) * Co, 256), 256, 0, st>>>(workspace, parts, L, Co, dw_oihw,
+                                                                                             dbias);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }

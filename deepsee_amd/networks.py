@@ -151,11 +151,14 @@ class NormConv:
     def conv(self, root):
         return self._get(root, self.conv_path)
 
-    def apply(self, root, x, w, act, training, **conv_kw):
-        """act(norm(conv(x, w))): w is the conv's spectral-normalised weight of this forward."""
+    def apply(self, root, x, w, act, training, conv=None, **conv_kw):
+        """act(norm(conv(x, w))): w is the conv's spectral-normalised weight of this forward.  `conv`: conv(w, bias) replaces
+        the dense convolution of x (the label-masked noise layer of StyleEncoder; x is then ignored)."""
         if self.norm == "none":
+            if conv is not None:
+                return ops.Act.apply(conv(w, self.conv(root).bias), act)
             return ops.conv2d(x, w, self.conv(root).bias, act=act, **conv_kw)
-        x = ops.conv2d(x, w, None, **conv_kw)
+        x = conv(w, None) if conv is not None else ops.conv2d(x, w, None, **conv_kw)
         if self.norm == "instance":
             return ops.InstNormAct.apply(x, act)
         bn = self._get(root, self.bn_path)
@@ -180,6 +183,13 @@ class Conv1dP(nn.Module):
 
 # ------------------------------------------------------------------------------------ noise / randomness
 EPOCH_STRIDE = 1 << 36          # stream positions reserved per forward (a forward draws < 2^31 float4s)
+_M64 = (1 << 64) - 1
+
+
+def eval_stream_seed(seed, pinned):
+    """Philox key of the eval-mode style-field stream: a fixed odd-multiplier transform of the model's noise seed (pinned False)
+    or of an explicit `style_seed` (pinned True), the two families kept apart by the low bit of the argument."""
+    return ((2 * int(seed) + int(bool(pinned))) * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03) & _M64
 _COIN_TAGS = {"enc_full": 0, "enc_noise": 1}
 _REGISTERED_EPOCH = None
 
@@ -201,6 +211,10 @@ class DeviceNoise:
         # in HBM, advanced by a device-side add at the start of every training forward -- so that a captured hipGraph,
         # whose kernel arguments (seed, offset) are frozen, still draws fresh noise on every replay.
         self.epoch = torch.zeros(1, dtype=torch.int64, device="cuda")
+        # eval-mode style fields (opt.random_style_matrix) draw from a second stream, positioned by a HOST counter that is not
+        # part of state_dict(): an eval forward between two training steps moves neither `offset` nor the device epoch
+        self.eval_count = 0
+        self._eval = [eval_stream_seed(self.seed, False), 0]
         self._register()
 
     def _register(self):
@@ -225,6 +239,31 @@ class DeviceNoise:
         self.offset = 0
         self.epoch.add_(EPOCH_STRIDE)
         self._register()
+
+    def begin_eval(self, style_seed=None):
+        """Start of an eval-mode forward (SRModel.forward for every mode but generator / discriminator).  Without `style_seed` the
+        forward gets the next EPOCH_STRIDE positions of the eval stream; with it, position 0 of the stream keyed by that seed,
+        and the counter stays: same seed, same labels -> the same style fields, bit for bit."""
+        if style_seed is None:
+            self.eval_count += 1
+            self._eval = [eval_stream_seed(self.seed, False), self.eval_count * EPOCH_STRIDE]
+        else:
+            self._eval = [eval_stream_seed(style_seed, True), 0]
+
+    def style_field(self, labels, training):
+        """The noise field of FullStyleEncoder under opt.random_style_matrix, one N(0,1) scalar per pixel of `labels`
+        (ops.Labels), as a lazily consumed stream (ops.PhiloxField).  Training: the ordinary (seed, offset, device epoch)
+        positions, (N H W + 3) // 4 of them -- a captured graph draws a fresh field on every replay.  Eval: the eval stream, its
+        (seed, offset) plain kernel arguments without the epoch."""
+        shape = (labels.n, labels.h, labels.w)
+        count = (labels.n * labels.h * labels.w + 3) // 4
+        if training:
+            f = ops.PhiloxField(shape, self.seed, self.offset, True, self)
+            self.offset += count
+        else:
+            f = ops.PhiloxField(shape, self._eval[0], self._eval[1], False)
+            self._eval[1] += count
+        return f
 
     def state_dict(self):
         """What a resumed run needs to CONTINUE the branch-coin and noise sequences instead of repeating them from the start
@@ -274,6 +313,17 @@ class ReplayNoise:
 
     def begin_step(self):
         pass
+
+    def begin_eval(self, style_seed=None):
+        pass
+
+    def style_field(self, labels, training):
+        """The reference's randn(N, label_nc, H, W) from the tape, gathered at every pixel's own class -> [N, H, W] (the other
+        channels are multiplied by zero)."""
+        v = self._next("normal", "style_field")
+        assert tuple(v.shape) == (labels.n, labels.nc, labels.h, labels.w), (tuple(v.shape), labels.nc)
+        idx = labels.t.long().clamp_(max=labels.nc - 1)[:, None]
+        return v.cuda().float().gather(1, idx)[:, 0].contiguous()
 
     def _next(self, kind, tag):
         k, t, v = self.tape[self.pos]
@@ -532,6 +582,13 @@ class StyleEncoder(nn.Module):
         nf, s = opt.nef, opt.regional_style_size
         self._sn = {}
         self.combined = opt.netE == "combinedstyle"
+        # encoder.py:116-120: FullStyleEncoder.forward replaces its input by randn(N, label_nc, crop, crop) * seg
+        self.random_style = bool(getattr(opt, "random_style_matrix", False))
+        if self.random_style and opt.netE != "fullstyle":
+            raise ValueError("random_style_matrix needs netE='fullstyle', got netE=%r: CombinedstyleEncoder.forward calls "
+                             "encoder_full.forward_main(x) directly (encoder.py:197-198), so the replacement of x by "
+                             "label-masked noise in FullStyleEncoder.forward (encoder.py:118-120) never runs there and the RGB "
+                             "image meets a convolution built for label_nc=%d input channels" % (opt.netE, opt.label_nc))
         self.scale = opt.noisy_style_scale
         self.dist = opt.noisy_style_dist
         if self.scale > 0:
@@ -545,7 +602,7 @@ class StyleEncoder(nn.Module):
             NormConv(self.encoder_mini, "final.0.0", s, 8 * nf, 3, norm)  # constructed, unused
         elif opt.netE == "fullstyle":
             # FullStyleEncoder keeps its layers at the root of the state dict
-            chans = [(nf, 3), (2 * nf, nf), (4 * nf, 2 * nf), (8 * nf, 4 * nf)]
+            chans = [(nf, opt.label_nc if self.random_style else 3), (2 * nf, nf), (4 * nf, 2 * nf), (8 * nf, 4 * nf)]
             self.norm_layers = [NormConv(self, nm, co, ci, 3, norm) for nm, (co, ci) in zip(FULL_NAMES, chans)]
         else:
             raise NotImplementedError("netE=%s (ministyle crashes in the reference too)" % opt.netE)
@@ -564,8 +621,14 @@ class StyleEncoder(nn.Module):
         if self.combined:
             x = (self.encoder_full if mode == "full" else self.encoder_mini).forward_main(x, training)
         else:
-            for nl, s, u in zip(self.norm_layers, [1, 2, 2, 1], [0, 0, 0, 1]):
-                x = nl.apply(self, x, nl.conv(self).weight(training), L.ACT_LRELU, training, stride=s, pad=1, ups=u)
+            first = None
+            if self.random_style:
+                # the image is ignored: the first layer reads (labels, one noise scalar per pixel) -- ops.OnehotNoiseConv3x3
+                field = noise.style_field(labels, training)
+                first = lambda w, b: ops.onehot_noise_conv3x3(labels, field, w, b)      # noqa: E731
+            for i, (nl, s, u) in enumerate(zip(self.norm_layers, [1, 2, 2, 1], [0, 0, 0, 1])):
+                x = nl.apply(self, x, nl.conv(self).weight(training), L.ACT_LRELU, training,
+                             conv=first if i == 0 else None, stride=s, pad=1, ups=u)
         x = self.final_layer.apply(self, x, self.final_layer.conv(self).weight(training), L.ACT_TANH, training)
         sm = ops.StylePool.apply(x, labels, labels.shift_for(x.shape[1], x.shape[2]))
         if self.scale > 0 and not no_noise:

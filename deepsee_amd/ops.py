@@ -299,6 +299,22 @@ class PhiloxNormal:
         return rng_fill(self.shape, self.seed, self.offset, True)
 
 
+class PhiloxField:
+    """One N(0,1) scalar per label pixel, [N, H, W], never materialised: the Philox stream (seed, offset) of dsee_rng_fill for an
+    [N,H,W,1] tensor, regenerated per tile by onehot_noise_conv3x3 (forward and weight gradient).  `use_epoch`: the device
+    epoch of `source` (a networks.DeviceNoise) offsets the stream, as for every training draw; False: (seed, offset) are
+    taken as they are -- the eval-mode stream, which must not depend on where training stands."""
+
+    def __init__(self, shape, seed, offset, use_epoch=True, source=None):
+        self.shape = tuple(shape)
+        self.seed, self.offset = int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1)
+        self.use_epoch, self.source = bool(use_epoch), source
+
+    def bind(self):
+        if self.use_epoch and self.source is not None:
+            self.source.ensure_registered()
+
+
 def _bind_rng(*streams):
     for e in streams:
         if isinstance(e, PhiloxNormal):
@@ -1514,6 +1530,55 @@ class SeanInput(torch.autograd.Function):
             ws = scratch(L.lib().dsee_label_segsum_workspace(n, lab.h, lab.w, shift, lab.nc, s), "seg")
             L.call("label_segsum", lab.t, dcat, ld, ctx.coff, dstyle, n, lab.h, lab.w, shift, lab.nc, s, 1.0, ws)
         return dw, db, dstyle, None, None, None, None
+
+
+def _field_args(field, shape):
+    """(tensor or None, seed, offset, use_epoch) of a noise field given as a device tensor [N,H,W] or a PhiloxField."""
+    if isinstance(field, PhiloxField):
+        assert field.shape == tuple(shape), "field %s for a label map %s" % (field.shape, tuple(shape))
+        field.bind()
+        return None, field.seed, field.offset, int(field.use_epoch)
+    assert isinstance(field, torch.Tensor) and field.is_cuda and field.dtype == torch.float32 \
+        and tuple(field.shape) == tuple(shape), "field: a float32 device tensor %s or a PhiloxField" % (tuple(shape),)
+    return field.contiguous(), 0, 0, 0
+
+
+class OnehotNoiseConv3x3(torch.autograd.Function):
+    """conv3x3(randn(N, nc, H, W) * one-hot(labels), weight) + bias -> NHWC [N,H,W,Co]: the first layer of FullStyleEncoder
+    under opt.random_style_matrix (encoder.py:116-120) as a 9-tap gather-sum over the label map with one noise scalar per
+    pixel (`field`: a device tensor [N,H,W] or a PhiloxField).  No data gradient (the input is noise): backward returns the
+    gradients of weight and bias only."""
+
+    @staticmethod
+    def forward(ctx, labels, field, weight, bias):
+        n, h, w, nc = labels.n, labels.h, labels.w, labels.nc
+        co = weight.shape[0]
+        assert tuple(weight.shape) == (co, nc, 3, 3), "weight %s for %d classes" % (tuple(weight.shape), nc)
+        f, seed, offset, use_epoch = _field_args(field, (n, h, w))
+        table = new(9, nc, co)
+        L.call("onehot_conv3x3_pack", weight.contiguous(), table, co, nc)
+        out = new(n, h, w, co)
+        L.call("onehot_noise_conv3x3_fwd", labels.t, f, C.c_uint64(seed), C.c_uint64(offset), use_epoch, table, bias, out,
+               n, h, w, nc, co)
+        out.dsee_layout = "nhwc"
+        ctx.labels, ctx.field, ctx.co, ctx.has_bias = labels, field, co, bias is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lab, co = ctx.labels, ctx.co
+        n, h, w, nc = lab.n, lab.h, lab.w, lab.nc
+        f, seed, offset, use_epoch = _field_args(ctx.field, (n, h, w))
+        dw = new(co, nc, 3, 3)
+        db = new(co) if ctx.has_bias else None
+        ws = scratch(L.lib().dsee_onehot_noise_conv3x3_wgrad_workspace(n, h, w, nc, co), "ohn")
+        L.call("onehot_noise_conv3x3_wgrad", lab.t, f, C.c_uint64(seed), C.c_uint64(offset), use_epoch, dout.contiguous(),
+               n, h, w, nc, co, dw, db, ws)
+        return None, None, dw, db
+
+
+def onehot_noise_conv3x3(labels, field_or_stream, weight, bias=None):
+    return OnehotNoiseConv3x3.apply(labels, field_or_stream, weight, bias)
 
 
 class StylePool(torch.autograd.Function):

@@ -2,7 +2,8 @@
 deepsee_models/sr_model.py::SRModel (SURVEY 8b): attributes netSR / netD / netE / opt / model_variant / logs /
 last_encoded_style_is_full / last_encoded_style_is_noisy; forward(data, mode) with modes 'generator', 'encode_only', 'demo',
 'discriminator', 'inference', 'baseline' and the six explorative modes of deepsee_amd.explore.MODES (anything else raises
-ValueError like sr_model.py:445-446); create_optimizers(opt);
+ValueError like sr_model.py:445-446; `style_seed=int` pins the eval-mode style field of opt.random_style_matrix);
+create_optimizers(opt);
 save(epoch) / load_weights().  All activation-space compute runs in libdeepsee_hip.so.
 """
 import math
@@ -159,6 +160,11 @@ class SRModel(nn.Module):
         d = self._native(data)
         if mode in ("generator", "discriminator"):
             self.noise.begin_step()     # fresh Philox positions / branch coins for this forward
+        else:
+            # eval-mode draws (the style field of opt.random_style_matrix) come from a stream of their own; style_seed pins it
+            begin_eval = getattr(self.noise, "begin_eval", None)    # (a caller's own noise object may only know begin_step)
+            if begin_eval is not None:
+                begin_eval(kwargs.get("style_seed"))
         if mode == "generator":
             g_loss, generated = self.compute_generator_loss(d)
             self.logs["image/downsized"] = d["image_lr"]
@@ -294,6 +300,13 @@ class SRModel(nn.Module):
         extra = set(state) - set(own)
         if missing or extra:
             raise RuntimeError("state dict mismatch: missing %s, unexpected %s" % (sorted(missing), sorted(extra)))
+        for k, v in own.items():
+            if tuple(state[k].shape) != tuple(v.shape) and state[k].numel() != v.numel():   # (a [1] for a [] is still taken)
+                hint = ""
+                if k.startswith("initial.") and v.dim() == 4 and state[k].dim() == 4 and state[k].shape[1] != v.shape[1]:
+                    hint = " (a style encoder's first layer has label_nc input channels with opt.random_style_matrix, 3 without)"
+                raise RuntimeError("state dict mismatch: %s is %s in the checkpoint, %s in this model%s"
+                                   % (k, list(state[k].shape), list(v.shape), hint))
         with torch.no_grad():
             for k, v in own.items():
                 v.copy_(state[k].to(v.device, v.dtype))

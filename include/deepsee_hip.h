@@ -637,6 +637,27 @@ size_t dsee_onehot_conv3x3_wgrad_workspace(int N, int H, int W, int shift, int L
 int dsee_onehot_conv3x3_wgrad(const uint8_t* lab, const float* dact, int dact_ld, const float* act, int act_ld, int N,
                               int H, int W, int shift, int L, float* dw_oihw, float* dbias, float* workspace,
                               hipStream_t stream);
+/* First layer of FullStyleEncoder under opt.random_style_matrix (encoder.py:116-120): conv3x3(randn(N,L,H,W) * one-hot(seg)).
+ * The masked input holds one scalar eps(n,y,x) per pixel, in the channel of the pixel's own class, so
+ *   out[n,y,x,co] = bias[co] + sum_{ky,kx} table[tap][lab(q)][co] * eps(q),   q = (n, y+ky-1, x+kx-1), zero padding,
+ * with table = dsee_onehot_conv3x3_pack(w) and out fp32 NHWC [N][H][W][Co] (Co % 4 == 0, Co / 4 a divisor of 256, the table
+ * plus a tile within 64 KB of LDS).  bias may be NULL.  A label >= L contributes nothing.  L <= 32.
+ * eps: field != NULL -- the tensor field[N][H][W]; field == NULL -- the Philox stream (seed, offset): pixel
+ * p = (n*H + y)*W + x is component p & 3 of the normal quadruple at position offset + (p >> 2), exactly what
+ * dsee_rng_fill(seed, offset, normal = 1) writes for an [N,H,W,1] tensor; use_epoch != 0 adds the registered device epoch
+ * (dsee_rng_set_epoch) as dsee_rng_fill does, use_epoch == 0 takes (seed, offset) as they are.  The field never reaches HBM. */
+int dsee_onehot_noise_conv3x3_fwd(const uint8_t* lab, const float* field, uint64_t seed, uint64_t offset, int use_epoch,
+                                  const float* table, const float* bias, float* out, int N, int H, int W, int L, int Co,
+                                  hipStream_t stream);
+/* Its weight gradient dw_oihw[co][c][ky][kx] = sum_q [lab(q) = c] eps(q) dout[q - tap][co] and (dbias != NULL)
+ * dbias[co] = sum_p dout[p][co]; dout fp32 [N][H][W][Co], Co % 4 == 0, 9 * Co <= 1024 and L accumulators per (tap, co) thread
+ * plus a tile within 64 KB of LDS (Co <= 48 at 32 classes, <= 80 at 19).  Per-block partials in `workspace`
+ * (dsee_onehot_noise_conv3x3_wgrad_workspace bytes), summed in a fixed order: no atomics, two calls are bit-identical, a
+ * class absent from the label map gets exactly 0.  There is no data gradient: the input is noise. */
+size_t dsee_onehot_noise_conv3x3_wgrad_workspace(int N, int H, int W, int L, int Co);
+int dsee_onehot_noise_conv3x3_wgrad(const uint8_t* lab, const float* field, uint64_t seed, uint64_t offset, int use_epoch,
+                                    const float* dout, int N, int H, int W, int L, int Co, float* dw_oihw, float* dbias,
+                                    float* workspace, hipStream_t stream);
 /* out[m][coff + r] = (label(m) == r), r in [0, 32): the one-hot input channels of the SEAN style table path */
 int dsee_label_onehot(const uint8_t* lab, float* out, int N, int H, int W, int shift, int out_ld, int coff,
                       hipStream_t stream);
