@@ -74,8 +74,10 @@ int dsee_sean_norm_fwd(const uint8_t* labels, int lab_h, int lab_w, int shift, i
                    "64 Winograd tiles of one image): N = %d, H = %d, W = %d", N, H, W);
     return DSEE_EUNSUPPORTED;
   }
-  if (label_nc < 1 || (table != nullptr && label_nc > 32)) {
-    dsee_set_error("dsee_sean_norm_fwd: label_nc = %d (the style-table path stores the one-hot label in 32 channels)", label_nc);
+  // (with and without table: the shared layer's weight gradient takes <= 32 classes too.  Like every check above it reads no
+  // pointer: tests/test_label_nc_host.py passes addresses that must never be dereferenced.)
+  if (label_nc < 1 || label_nc > 32) {
+    dsee_set_error("dsee_sean_norm_fwd: label_nc = %d (1..32: the one-hot label is stored in 32 channels)", label_nc);
     return DSEE_EUNSUPPORTED;
   }
   if (!training && !(running_mean && running_var)) {
@@ -282,7 +284,9 @@ BlockSaved saved_layout(Arena& a, int N, int H, int W, int C, int has_t) {
   return s;
 }
 
-int train_shape_ok(const char* who, int N, int H, int W, int C, int label_nc, int has_t) {
+// (Only arithmetic on the scalar arguments: tests/test_label_nc_host.py calls the entry points with addresses that must never be
+// dereferenced and relies on these checks, like the NULL checks before them, coming before the first use of a pointer.)
+int train_shape_ok(const char* who, int N, int H, int W, int C, int label_nc) {
   const long T = (long)N * (H / 4) * (W / 4);
   if (N <= 0 || H % 4 || W % 4 || ((H / 4) * (W / 4)) % 64 || T % 256 || C % 256 || (C & (C - 1)) ||
       (36 * T / 256) * (C / 256) < 512 || 256 % (C / 4) != 0) {
@@ -290,8 +294,8 @@ int train_shape_ok(const char* who, int N, int H, int W, int C, int label_nc, in
                    "%% 64 == 0 and at least 512 GEMM tiles (36 T / 256 x C / 256): N = %d, H = %d, W = %d, C = %d", who, N, H, W, C);
     return DSEE_EUNSUPPORTED;
   }
-  if (label_nc < 1 || (has_t && label_nc > 32)) {
-    dsee_set_error("%s: label_nc = %d", who, label_nc);
+  if (label_nc < 1 || label_nc > 32) {     // (with and without table: dsee_onehot_conv3x3_wgrad and the 32 one-hot channels)
+    dsee_set_error("%s: label_nc = %d (1..32: the one-hot label is stored in 32 channels)", who, label_nc);
     return DSEE_EUNSUPPORTED;
   }
   return DSEE_OK;
@@ -367,7 +371,7 @@ int dsee_spade_resblock_train_fwd(const dsee_norm_layer* norm_0, const float* w_
     dsee_set_error("%s: the label map (%d x %d >> %d) does not cover the %d x %d feature map", who, lab_h, lab_w, shift, H, W);
     return DSEE_EINVAL;
   }
-  DSEE_TRY(train_shape_ok(who, N, H, W, C, label_nc, has_t));
+  DSEE_TRY(train_shape_ok(who, N, H, W, C, label_nc));
   Arena sa = {static_cast<char*>(saved), 0}, wa = {static_cast<char*>(workspace), 0};
   const BlockSaved S = saved_layout(sa, N, H, W, C, has_t);
   const FwdScratch F = fwd_scratch(wa, N, H, W, C, label_nc, has_t);
@@ -492,7 +496,7 @@ int dsee_spade_resblock_bwd(const dsee_norm_layer* norm_0, const float* w_conv_0
     return DSEE_EINVAL;
   }
   const int has_t = norm_0->table != nullptr;
-  DSEE_TRY(train_shape_ok(who, N, H, W, C, label_nc, has_t));
+  DSEE_TRY(train_shape_ok(who, N, H, W, C, label_nc));
   Arena sa = {const_cast<char*>(static_cast<const char*>(saved)), 0}, wa = {static_cast<char*>(workspace), 0};
   const BlockSaved S = saved_layout(sa, N, H, W, C, has_t);
   const BwdScratch B = bwd_scratch(wa, N, H, W, C, label_nc, has_t, lab_h, lab_w, shift);

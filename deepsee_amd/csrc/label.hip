@@ -8,6 +8,13 @@
 //  * label_segsum:   S[b,r,c] = scale * sum_{hw: label=r} f[b,h,w,c]   (encoder.py:36-49 extract_style_matrix,
 //    divides by H*W not by region area), also the backward of label_gather.
 //  * nearest resize of the label map is index math: src = dst << shift  (F.interpolate 'nearest', SURVEY B-3).
+//
+// Labels outside [0, L): a pixel whose byte is >= L (the loader's "unknown" 255 -> label_nc without a dontcare class, or any
+// stray value) is an ALL-ZERO one-hot vector in every kernel here -- it adds no table row to a gather-sum, gathers a zero
+// style row, and is skipped by the segmented sums -- as in build_d_input and the compare-select weight gradient.  (The
+// reference raises in scatter_ instead.)  No address is ever formed from such a byte: every table index below sits behind
+// `(unsigned)r < (unsigned)L`.  The 32 one-hot columns (dsee_label_onehot, onehot_coff) flag the raw byte when it is < 32;
+// their consumers multiply columns >= L by zero table columns.
 #include "dsee_common.h"
 #include "dsee_rng.h"
 
@@ -43,7 +50,7 @@ __global__ __launch_bounds__(256) void onehot_conv_fwd_kernel(const uint8_t* __r
           if (hh >= 0 && hh < R && ww >= 0 && ww < Rw) {
             const int r = lab_at(lab, n, H, W, shift, hh, ww);
             const int tap = (dy + 1) * 3 + (dx + 1);
-            acc += *reinterpret_cast<const f32x4*>(wt + ((size_t)tap * L + r) * Co + q * 4);
+            if (r < L) acc += *reinterpret_cast<const f32x4*>(wt + ((size_t)tap * L + r) * Co + q * 4);
           }
         }
       if (relu) {
@@ -104,7 +111,8 @@ __global__ __launch_bounds__(1024) void onehot_conv_fwd_lds_kernel(const uint8_t
       f32x4 acc = b;
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap)
-        if (cur[tap] >= 0) acc += *reinterpret_cast<const f32x4*>(tab + ((size_t)tap * L + cur[tap]) * Co + q * 4);
+        if ((unsigned)cur[tap] < (unsigned)L)    // (-1 outside the image, >= L: no row)
+          acc += *reinterpret_cast<const f32x4*>(tab + ((size_t)tap * L + cur[tap]) * Co + q * 4);
       if (relu) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) acc[k] = fmaxf(acc[k], 0.f);
@@ -167,7 +175,7 @@ __global__ __launch_bounds__(1024) void onehot_conv_fwd_lds4_kernel(const uint8_
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
           const int r = win[tap / 3][p + tap % 3];
-          if (r >= 0) acc += *reinterpret_cast<const f32x4*>(tq + (tap * L + r) * Co);
+          if ((unsigned)r < (unsigned)L) acc += *reinterpret_cast<const f32x4*>(tq + (tap * L + r) * Co);
         }
         if (relu) {
 #pragma unroll
@@ -297,7 +305,7 @@ __global__ __launch_bounds__(256) void label_onehot_kernel(const uint8_t* __rest
   }
 }
 
-// out[m][ld] @coff = scale * table[n][lab(m)][:]
+// out[m][ld] @coff = scale * table[n][lab(m)][:]   (zeros where lab(m) >= L)
 __global__ __launch_bounds__(256) void label_gather_kernel(const uint8_t* __restrict__ lab,
                                                            const float* __restrict__ table, float* __restrict__ out,
                                                            int N, int H, int W, int shift, int R, int Rw, int L, int Cs,
@@ -311,12 +319,13 @@ __global__ __launch_bounds__(256) void label_gather_kernel(const uint8_t* __rest
     const unsigned mu_ = (unsigned)m, t_ = mu_ / (unsigned)Rw, n_ = t_ / (unsigned)R;
     const int w = (int)(mu_ - t_ * (unsigned)Rw), h = (int)(t_ - n_ * (unsigned)R), n = (int)n_;
     const int r = lab_at(lab, n, H, W, shift, h, w);
-    f32x4 v = *reinterpret_cast<const f32x4*>(table + ((size_t)n * L + r) * Cs + q * 4) * scale;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (r < L) v = *reinterpret_cast<const f32x4*>(table + ((size_t)n * L + r) * Cs + q * 4) * scale;
     *reinterpret_cast<f32x4*>(out + m * ld + coff + q * 4) = v;
   }
 }
 
-// part[n][chunk][L][Cs] = sum_{pixels of chunk with label r} in[m][coff + c]
+// part[n][chunk][L][Cs] = sum_{pixels of chunk with label r} in[m][coff + c]   (pixels with a label >= L enter no sum)
 __global__ __launch_bounds__(256) void label_segsum_kernel(const uint8_t* __restrict__ lab,
                                                            const float* __restrict__ in, int ld, int coff, int H, int W,
                                                            int shift, int R, int Rw, int L, int Cs, int chunk_px,
@@ -333,7 +342,7 @@ __global__ __launch_bounds__(256) void label_segsum_kernel(const uint8_t* __rest
     for (int p = p0 + s; p < p1; p += slots) {
       const int h = p / Rw, w = p % Rw;
       const int r = lab_at(lab, n, H, W, shift, h, w);
-      accs[(s * L + r) * Cs + c] += in[((size_t)n * P + p) * ld + coff + c];
+      if (r < L) accs[(s * L + r) * Cs + c] += in[((size_t)n * P + p) * ld + coff + c];
     }
   }
   __syncthreads();
@@ -642,7 +651,7 @@ int dsee_onehot_noise_conv3x3_fwd(const uint8_t* lab, const float* field, uint64
   DSEE_CHECK_ARG(Co > 0 && Co % 4 == 0 && 256 % (Co / 4) == 0);
   DSEE_CHECK_ARG((long)N * H * W < (1L << 31));
   const size_t lds = (size_t)9 * L * Co * sizeof(float) + (size_t)NZ_HALO * (sizeof(float) + sizeof(int));
-  DSEE_CHECK_ARG(lds <= 64 * 1024);      // (the whole tap table sits in LDS: Co <= 48 at 32 classes, <= 80 at 19)
+  DSEE_CHECK_ARG(lds <= 64 * 1024);      // (the whole tap table sits in LDS: with Co / 4 dividing 256 that is Co <= 32 at 32 classes, <= 64 at 19)
   int tx, ty;
   const int tiles = noise_tiles(N, H, W, &tx, &ty);
   onehot_noise_fwd_kernel<<<tiles, 256, lds, st>>>(lab, field, seed, offset, (use_epoch && !field) ? dsee_rng_epoch() : nullptr,

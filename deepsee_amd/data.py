@@ -218,7 +218,7 @@ def device_preprocess(opt, batch, stream=None):
         n, h, w = u8.shape
         out = torch.empty_like(u8)
         L.call("label_u8_prepare", u8, flip, out, n, h, w, opt.label_nc)
-        return ops.Labels(out, opt.label_nc)
+        return ops.Labels(out, opt.semantic_nc)
 
     hr = image(batch["image"])
     res = {"input_semantics": labels(batch["label"]), "image_hr": hr, "image_lr": ops.lr_image(opt, hr)}

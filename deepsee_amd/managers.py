@@ -44,13 +44,13 @@ class BaseManager:
         opt = self.opt
         image = ops.to_nhwc(out["image"])
         res = {
-            "input_semantics": ops.Labels(ops.label_to_u8(out["label"]), opt.label_nc),
+            "input_semantics": ops.Labels(ops.label_to_u8(out["label"]), opt.semantic_nc),
             "image_lr": ops.lr_image(opt, image),
             "image_hr": image,
         }
         if opt.guiding_style_image:
             res["guiding_image"] = ops.to_nhwc(out["guiding_image"])
-            res["guiding_label"] = ops.Labels(ops.label_to_u8(out["guiding_label"]), opt.label_nc)
+            res["guiding_label"] = ops.Labels(ops.label_to_u8(out["guiding_label"]), opt.semantic_nc)
         return res
 
 

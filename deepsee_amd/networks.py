@@ -591,6 +591,16 @@ class StyleEncoder(nn.Module):
                              "image meets a convolution built for label_nc=%d input channels" % (opt.netE, opt.label_nc))
         self.scale = opt.noisy_style_scale
         self.dist = opt.noisy_style_dist
+        if opt.semantic_nc != opt.label_nc and (self.scale > 0 or self.random_style):
+            # the reference fails in its first training forward pass here: the style matrix has semantic_nc rows and the corruption
+            # indexes the label_nc noise weights with them (encoder.py:54-56, IndexError); the random style field is
+            # randn(N, seg.size(1) = semantic_nc, ..) * seg, fed to a first convolution built for label_nc input channels
+            # (encoder.py:78, 119).  There is no training behaviour to reproduce: refuse at build (which also rules out the one use
+            # the reference could run, inference with the corruption switched off by no_noise).
+            raise ValueError("contain_dontcare_label (semantic_nc=%d, label_nc=%d) needs noisy_style_scale=0 and no "
+                             "random_style_matrix: the encoder has label_nc noise weights and a label_nc-channel first layer for "
+                             "semantic_nc regions / noise channels (the reference raises in encoder.py:56 / :120)"
+                             % (opt.semantic_nc, opt.label_nc))
         if self.scale > 0:
             self.noise_weights = nn.Parameter(torch.zeros(opt.label_nc))
         self.norm = norm = nonspade_norm_of(getattr(opt, "norm_E", "spectralinstance"))
@@ -651,7 +661,7 @@ class NLayerD(nn.Module):
     def __init__(self, opt):
         super().__init__()
         nf = opt.ndf
-        cin = opt.label_nc + opt.output_nc + (1 if opt.contain_dontcare_label else 0)
+        cin = opt.semantic_nc + opt.output_nc         # (what ops.DInput writes: Labels.nc one-hot channels + the image)
         self.nl = opt.n_layers_D
         self.norm = nonspade_norm_of(getattr(opt, "norm_D", "spectralinstance"))
         attach(self, "model0.0", ConvP(nf, cin, 4))

@@ -259,13 +259,25 @@ def bicubic_up(img_nhwc, h, w, clamp=True):
     return y
 
 
+MAX_LABELS = 32      # one-hot columns of every per-image table and of dsee_label_onehot; L <= 32 in the label kernels
+
+
+def check_label_count(nc):
+    """ValueError unless 1 <= nc <= MAX_LABELS.  Raised where a model or a label map is BUILT, so that no pass can fail
+    half-way (a forward that succeeds and a backward that stops after other gradients were written)."""
+    if not 1 <= int(nc) <= MAX_LABELS:
+        raise ValueError("%d semantic classes: the kernels keep the one-hot label in %d columns (1 <= semantic_nc <= %d)"
+                         % (nc, MAX_LABELS, MAX_LABELS))
+    return int(nc)
+
+
 class Labels:
     """uint8 HR label map + the shift for a given resolution (nearest resize as index math)."""
 
     def __init__(self, lab_u8, nc):
         self.t = lab_u8
         self.n, self.h, self.w = lab_u8.shape
-        self.nc = nc
+        self.nc = check_label_count(nc)      # (so every consumer below, forward and backward, sees 1..32 classes)
 
     def shift_for(self, r, rw=None):
         """Shift that maps an r x rw feature map (rw None: the same fraction of the width) onto the label map.  Both axes must be
@@ -2177,7 +2189,7 @@ class SeanNormTable(torch.autograd.Function):
                     g1 = torch.empty_like(dactv)
                     tag_amax(g1, amax_slot())
                     L.call("act_bwd_amax", dactv.contiguous(), act_lo, g1, C.c_long(g1.numel()), L.ACT_RELU, LRELU_SLOPE, g1.dsee_amax)
-                    oh = new(n, rh, rw_, 32)
+                    oh = new(n, rh, rw_, MAX_LABELS)     # (lab.nc <= MAX_LABELS: Labels checks it where the map is built)
                     L.call("label_onehot", lab.t, oh, n, lab.h, lab.w, shift, 32, 0)
                     dw_sh = wgrad_raw(oh, g1, L.geom_fwd(n, rh, rw_, 32, NHIDDEN, 3, 1, 1, 0), NHIDDEN, lab.nc, 3, 3)
                     db_sh = channel_dot(g1, None, NHIDDEN).clone()

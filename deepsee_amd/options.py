@@ -8,7 +8,7 @@ DEFAULTS = dict(
     norm_G="spectrallateseansyncbatch3x3", norm_D="spectralinstance", norm_E="spectralinstance",
     add_noise=True, noisy_style_scale=0.2, noisy_style_dist="uniform",
     batchSize=8, load_size=256, crop_size=256, start_size=32, aspect_ratio=1.0,
-    label_nc=19, contain_dontcare_label=False, semantic_nc=19, output_nc=3,
+    label_nc=19, contain_dontcare_label=False, output_nc=3,   # (semantic_nc is derived: make_opt)
     max_fm_size=256, downsampling_method="bicubic",
     netG="deepsee", netE="combinedstyle", netD="multiscale", netD_subarch="n_layer",
     ngf=32, nef=32, ndf=32, num_D=2, n_layers_D=4,
@@ -57,4 +57,9 @@ def make_opt(preset=None, **over):
     if preset:
         d.update(PRESETS[preset])
     d.update(over)
+    # options/base_options.py:231-234: the one-hot label tensor has one more channel when the maps hold a "don't care" value
+    nc = d["label_nc"] + (1 if d["contain_dontcare_label"] else 0)
+    if d.setdefault("semantic_nc", nc) != nc:
+        raise ValueError("semantic_nc=%r contradicts label_nc=%d with contain_dontcare_label=%s (it is derived: %d)"
+                         % (d["semantic_nc"], d["label_nc"], d["contain_dontcare_label"], nc))
     return SimpleNamespace(**d)

@@ -99,6 +99,7 @@ def _sum_terms(terms):
 class SRModel(nn.Module):
     def __init__(self, opt):
         super().__init__()
+        ops.check_label_count(opt.semantic_nc)       # (before anything is allocated: > 32 classes can only fail later, mid-pass)
         if not torch.cuda.is_available():
             raise RuntimeError("deepsee_amd.SRModel needs an MI355X (HIP) device: there is no CPU fallback")
         L.lib()  # fail loudly if libdeepsee_hip.so is missing
@@ -324,11 +325,11 @@ class SRModel(nn.Module):
         sem = data.get("input_semantics")
         if isinstance(sem, torch.Tensor):
             lab = sem.argmax(1, keepdim=True).float()
-            sem = ops.Labels(ops.label_to_u8(lab.cuda()), self.opt.label_nc)
+            sem = ops.Labels(ops.label_to_u8(lab.cuda()), self.opt.semantic_nc)
         d["labels"] = sem
         gl = data.get("guiding_label")
         if isinstance(gl, torch.Tensor):
-            gl = ops.Labels(ops.label_to_u8(gl.argmax(1, keepdim=True).float().cuda()), self.opt.label_nc)
+            gl = ops.Labels(ops.label_to_u8(gl.argmax(1, keepdim=True).float().cuda()), self.opt.semantic_nc)
         d["guiding_labels"] = gl
         for k in ("image_lr", "image_hr", "guiding_image"):
             v = data.get(k)

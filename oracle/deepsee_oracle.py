@@ -43,7 +43,7 @@ def make_opt(**over):
         norm_G="spectrallateseansyncbatch3x3", norm_D="spectralinstance", norm_E="spectralinstance",
         add_noise=True, noisy_style_scale=0.2, noisy_style_dist="uniform",
         batchSize=8, load_size=256, crop_size=256, start_size=32, aspect_ratio=1.0,
-        label_nc=19, contain_dontcare_label=False, semantic_nc=19, output_nc=3,
+        label_nc=19, contain_dontcare_label=False, output_nc=3,   # (semantic_nc is derived below)
         max_fm_size=256, downsampling_method="bicubic",
         netG="deepsee", netE="combinedstyle", netD="multiscale", netD_subarch="n_layer",
         ngf=32, nef=32, ndf=32, num_D=2, n_layers_D=4,
@@ -56,6 +56,11 @@ def make_opt(**over):
         niter=50, niter_decay=25, gpu_info=False, checkpoints_dir="./checkpoints",
     )
     d.update(over)
+    # options/base_options.py:231-234
+    nc = d["label_nc"] + (1 if d["contain_dontcare_label"] else 0)
+    if d.setdefault("semantic_nc", nc) != nc:
+        raise ValueError("semantic_nc=%r contradicts label_nc=%d with contain_dontcare_label=%s (it is derived: %d)"
+                         % (d["semantic_nc"], d["label_nc"], d["contain_dontcare_label"], nc))
     return SimpleNamespace(**d)
 
 
@@ -135,7 +140,7 @@ def sr_spec(opt):
 
 def d_spec(opt):
     spec = OrderedDict()
-    cin0 = opt.label_nc + opt.output_nc + (1 if opt.contain_dontcare_label else 0)
+    cin0 = opt.semantic_nc + opt.output_nc       # (networks/discriminator.py: label_nc + output_nc, + 1 with a dontcare label)
     for i in range(opt.num_D):
         p = "discriminator_%d" % i
         nf = opt.ndf
@@ -799,13 +804,13 @@ class Oracle:
         opt, dt = self.opt, self.dtype
         img = batch["image"].to(dt)
         out = {
-            "input_semantics": onehot_labels(batch["label"], opt.label_nc, dt),
+            "input_semantics": onehot_labels(batch["label"], opt.semantic_nc, dt),    # data/preprocessor.py:37-38
             "image_lr": bicubic_down(img, opt.start_size),
             "image_hr": img,
         }
         if opt.guiding_style_image:
             out["guiding_image"] = batch["guiding_image"].to(dt)
-            out["guiding_label"] = onehot_labels(batch["guiding_label"], opt.label_nc, dt)
+            out["guiding_label"] = onehot_labels(batch["guiding_label"], opt.semantic_nc, dt)
         return out
 
     def params(self, net):
@@ -906,14 +911,14 @@ class Oracle:
 
 # --------------------------------------------------------------------------- synthetic batches
 def synthetic_batch(opt, n, seed=1234, guided=None):
-    """blocky 19-class label map (16x16 cells, nearest-upsampled) and
-    uniform [-1,1] image, all seeded."""
+    """blocky label map (16x16 cells, nearest-upsampled; the classes [0, label_nc) and, with
+    contain_dontcare_label, the value label_nc too) and uniform [-1,1] image, all seeded."""
     g = torch.Generator().manual_seed(seed)
     h = opt.crop_size
     cells = min(16, h)
 
     def lab():
-        c = torch.randint(0, opt.label_nc, (n, 1, cells, cells), generator=g).float()
+        c = torch.randint(0, opt.semantic_nc, (n, 1, cells, cells), generator=g).float()
         return F.interpolate(c, size=(h, h), mode="nearest")
 
     batch = {"label": lab(), "image": torch.rand(n, 3, h, h, generator=g) * 2 - 1}

@@ -53,6 +53,14 @@ CASES = {
     # no-noise, no-TTUR, gradient clipping on
     "indep_clip_4to32_ngf8": dict(opt=dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8,
                                            add_noise=False, no_TTUR=True, gradient_clip=0.01), n=2, seed=16, iters=1),
+    # class counts other than 19: a dontcare label (semantic_nc = label_nc + 1 = 20 one-hot channels, the synthetic batch draws
+    # from [0, label_nc] inclusive; options/base_options.py:231-234, data/preprocessor.py:37-38) and a small label_nc.
+    # noisy_style_scale = 0: with the style corruption on, the reference indexes its label_nc noise weights with the semantic_nc
+    # rows of the style matrix (encoder.py:54-56) and raises IndexError in the first forward pass.
+    "dontcare_4to32_bs2_ngf8": dict(opt=dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8,
+                                             contain_dontcare_label=True, noisy_style_scale=0.0), n=2, seed=18, iters=1),
+    "label5_4to32_bs2_ngf8": dict(opt=dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8, label_nc=5),
+                                  n=2, seed=19, iters=1),
 }
 
 

@@ -89,8 +89,13 @@ FLAGS = [dict(clamp=c, recurrent=r, noise=z, same=s, mask=m)
 
 @pytest.mark.parametrize("f", FLAGS, ids=lambda f: "-".join("%s%s" % (k[0], v) for k, v in f.items()))
 def test_style_explore_equals_the_torch_rule(f):
+    style_explore_equals_the_torch_rule(f)
+
+
+def style_explore_equals_the_torch_rule(f, nc=19):
+    """(the body, with the class count as an argument: tests/test_gpu_label_nc.py runs it at other counts than 19)"""
     from deepsee_amd import explore
-    B, n, nc, S = 2, 4, 19, 128
+    B, n, S = 2, 4, 128
     g = torch.Generator().manual_seed(11)
     s0 = torch.rand(B, nc, S, generator=g) * 3 - 1.5
     s1 = s0 if f["same"] else torch.rand(B, nc, S, generator=g) * 3 - 1.5

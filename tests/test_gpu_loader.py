@@ -76,6 +76,13 @@ def test_raw_device_preprocess_per_mode(name):
     assert torch.equal(got["image_hr"], want["image_hr"]) and torch.equal(got["image_lr"], want["image_lr"])
     assert torch.equal(got["input_semantics"].t, want["input_semantics"].t)
     assert int(want["input_semantics"].t.max()) == 19                        # the 255 of the label files arrived as label_nc
+    # ... which is outside [0, nc) without a dontcare class (an all-zero one-hot vector in every kernel: label.hip,
+    # tests/test_gpu_label_nc.py) and class 19 of 20 with one
+    assert want["input_semantics"].nc == 19
+    from deepsee_amd.options import make_opt
+    dc = make_opt(**dict({k: v for k, v in vars(opt).items() if k != "semantic_nc"}, contain_dontcare_label=True))
+    with_dc = D.device_preprocess(dc, wire)
+    assert with_dc["input_semantics"].nc == 20 and torch.equal(with_dc["input_semantics"].t, want["input_semantics"].t)
     raw.update(guiding_image_raw=raw["image_raw"], guiding_label_raw=raw["label_raw"])
     guided = D.device_preprocess(opt, raw)
     assert torch.equal(guided["guiding_image"], want["image_hr"]) and torch.equal(guided["guiding_label"].t, want["input_semantics"].t)

@@ -29,6 +29,13 @@ CASES = {
                                  max_fm_size=64),
     "clip_nottur_4to32": dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8, add_noise=False,
                               no_TTUR=True, gradient_clip=0.01),
+    # class counts other than 19 (tests/golden/dontcare_4to32_bs2_ngf8.json and label5_4to32_bs2_ngf8.json pin the oracle of the
+    # first two against the reference): a dontcare label -- 20 one-hot channels, label value 19 in range, D's first layer 23 wide,
+    # without style corruption as the reference can only run it --, five classes, and 32: every 32-column table full
+    "dontcare_4to32_ngf8": dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8, contain_dontcare_label=True,
+                                noisy_style_scale=0.0),
+    "label5_4to32_ngf8": dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8, label_nc=5),
+    "label32_4to32_ngf8": dict(start_size=4, crop_size=32, load_size=32, batchSize=2, ngf=8, label_nc=32),
     # (the benchmark's geometry with a batch > 1 -- BatchNorm over several images, per-image style-table groups, the Winograd
     # chunking of a batch -- is held against the oracle at the benchmark's own bs = 8 x 512 channels by
     # test_benchmark_path_matches_oracle, whose first occurrence of every graph is this eager path; the 128-channel bs = 4 case of
@@ -166,6 +173,41 @@ def test_train_step_matches_oracle(name):
                 if "%s.%s" % (net, k) not in zero_grad:   # (analytically-zero gradients are all noise)
                     assert float(dlt.mean()) <= 4e-5, (net, k, float(dlt.mean()))
     print("G-grad rel err: median %.2e max %.2e; D-grad max %.2e" % (errs[len(errs) // 2], errs[-1], derrs[-1]))
+
+
+@pytest.mark.parametrize("name", ["dontcare_4to32_ngf8", "label5_4to32_ngf8", "label32_4to32_ngf8"])
+def test_class_count_replayed_graphs_track_eager(name):
+    """The class-count cases of test_train_step_matches_oracle on the default path: six G+D iterations with hip_graphs on (eager,
+    capture, replays) against the same model stepped eagerly -- the yardstick of
+    test_hip_graphs_default_on_partial_batches_and_shape_eviction."""
+    from deepsee_amd.managers import TrainerManager
+    from deepsee_amd.options import make_opt
+    over = dict(CASES[name], seed=21)
+    batch = O.synthetic_batch(O.make_opt(**CASES[name]), 2, seed=31)
+    assert int(batch["label"].max()) == make_opt(**over).semantic_nc - 1
+    iters = 6
+
+    def run(**kw):
+        tm = TrainerManager(make_opt(**over, **kw))
+        out = []
+        for _ in range(iters):
+            tm.run_generator_one_step({k: v.clone() for k, v in batch.items()})
+            tm.run_discriminator_one_step({k: v.clone() for k, v in batch.items()})
+            out.append({k: float(v) for k, v in tm.get_latest_losses().items()})
+        torch.cuda.synchronize()
+        flat = (tm.optimizer_G.flat.detach().cpu().clone(), tm.optimizer_D.flat.detach().cpu().clone())
+        stats = dict(tm.graph_stats)
+        tm.close()
+        return out, flat, stats
+
+    eager, graphs = run(hip_graphs=False), run()
+    assert eager[2]["replayed"] == 0 and graphs[2]["captured"] >= 2 and graphs[2]["replayed"] >= 2, graphs[2]
+    for it, (a, b) in enumerate(zip(eager[0], graphs[0])):
+        for k in a:
+            assert abs(a[k] - b[k]) <= 2e-3 * abs(a[k]) + 1e-6, (it, k, a[k], b[k])
+    for x, y in zip(eager[1], graphs[1]):
+        assert float((x - y).abs().max()) <= 2.5 * iters * 4e-4, float((x - y).abs().max())
+        assert float((x - y).abs().mean()) <= 5e-5, float((x - y).abs().mean())
 
 
 @pytest.mark.parametrize("name,over", [

@@ -45,14 +45,28 @@ def _rect(*vals):
                                         # rectangular, label map 4x the feature map on both axes (32 x 64 / 64 x 32)
                                         _rect("sean", 64, (8, 16), 2), _rect("spade", 8, (16, 8), 2)])
 def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
+    spade_sean_norm_fwd_bwd(kind, C, R, N)
+
+
+def _dense_onehot(label, Lc):
+    """one-hot of a float label map [N,1,H,W] as a comparison, so that a value >= Lc is an all-zero vector (O.onehot_labels
+    scatters, and raises for such a map as the reference does); equal to O.onehot_labels on an in-range map"""
+    return (label.long() == torch.arange(Lc)[None, :, None, None]).float()
+
+
+def spade_sean_norm_fwd_bwd(kind, C, R, N, Lc=19, label=None):
+    """(the body, with the class count and optionally the label map [N,1,H,W] as arguments: tests/test_gpu_label_nc.py runs it at
+    other counts than 19 and on maps with absent classes / values >= Lc)"""
     from deepsee_amd import ops, lib as L
     square = isinstance(R, int)
     R, Rw = _hw(R)
     g = gen(C * R + N)
-    Lc, S = 19, 128
+    S = 128
     H, W = (32, 32) if square else (4 * R, 4 * Rw)
-    label = torch.randint(0, Lc, (N, 1, H, W), generator=g).float()
-    seg = O.onehot_labels(label, Lc)
+    drawn = torch.randint(0, Lc, (N, 1, H, W), generator=g).float()
+    label = drawn if label is None else label
+    assert tuple(label.shape) == (N, 1, H, W)
+    seg = _dense_onehot(label, Lc)
     style = (torch.rand(N, Lc, S, generator=g) * 2 - 1).requires_grad_()
     x = torch.randn(N, C, R, Rw, generator=g).requires_grad_()
     spec = {"n.param_free_norm.running_mean": (C,), "n.param_free_norm.running_var": (C,),
@@ -124,6 +138,14 @@ def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
     for k, v in P.items():
         if v.requires_grad and v.grad is not None and k in p:
             assert rel(p[k].grad.cpu(), v.grad) < 1e-4, k
+    # a class that no pixel of the (resized) map of image b holds: exactly zero rows in the style gradient and in dw_shared
+    low = label[:, 0, ::H // R, ::W // Rw].long()
+    gone = torch.stack([torch.bincount(im[im < Lc].reshape(-1), minlength=Lc) == 0 for im in low])
+    if want_style:
+        assert float(sty.grad.cpu()[gone].abs().sum()) == 0.0 and float(style.grad[gone].abs().sum()) == 0.0
+    if want_actv:
+        assert float(p["n.mlp_shared.0.weight"].grad.cpu()[:, gone.all(0)].abs().sum()) == 0.0
+    return gone
 
 
 @pytest.mark.parametrize("kind,C,R,N,max_fm", [
@@ -139,7 +161,13 @@ def test_spade_sean_norm_fwd_bwd(kind, C, R, N):
     _rect("sean", 64, (32, 64, True), 2, 256), _rect("spade", 64, (64, 32, True), 2, 256),
     _rect("puresean", 64, (32, 64, True), 2, 256)])
 def test_sean_norm_table_path(kind, C, R, N, max_fm):
-    """The production path for R >= 16: style half as per-image one-hot tables (K = 1440 instead of 2304).  From R = 64
+    sean_norm_table_path(kind, C, R, N, max_fm)
+
+
+def sean_norm_table_path(kind, C, R, N, max_fm, Lc=19, label=None):
+    """(The body, with the class count and optionally the label map [N,1,H,W] as arguments: tests/test_gpu_label_nc.py runs it at
+    other counts than 19 and on maps with absent classes / values >= Lc.)
+    The production path for R >= 16: style half as per-image one-hot tables (K = 1440 instead of 2304).  From R = 64
     the gamma/beta GEMM, its data gradient and its weight/table gradient run in the Winograd F(4x4,3x3) domain with
     (transform position, image) groups: ~10x the fp32 rounding error of the direct form, and the ReLU / LeakyReLU
     masks taken from values within that error of zero flip (a sqrt(fraction) effect on the gradients)."""
@@ -148,9 +176,11 @@ def test_sean_norm_table_path(kind, C, R, N, max_fm):
     wino_want = R >= 64 if isinstance(R, int) else R[2]
     (R, Rw), (H, W) = _hw(R), ((64, 64) if isinstance(R, int) else (2 * R[0], 2 * R[1]))
     g = gen(7 * C + R + N)
-    Lc, S = 19, 128
-    label = torch.randint(0, Lc, (N, 1, H, W), generator=g).float()
-    seg = O.onehot_labels(label, Lc)
+    S = 128
+    drawn = torch.randint(0, Lc, (N, 1, H, W), generator=g).float()
+    label = drawn if label is None else label
+    assert tuple(label.shape) == (N, 1, H, W)
+    seg = _dense_onehot(label, Lc)
     style = (torch.rand(N, Lc, S, generator=g) * 2 - 1).requires_grad_()
     x = torch.randn(N, C, R, Rw, generator=g).requires_grad_()
     mod = Nw.SpadeNorm(kind, C, Lc, S, max_fm)
@@ -168,7 +198,21 @@ def test_sean_norm_table_path(kind, C, R, N, max_fm):
     capped = kind != "spade" and max_fm < R
     wino = ops._wino_mod_chunk(N, R, Rw, C, 2 * C, kind != "spade" and not capped) is not None
     assert wino == wino_want
-    h = mod(xs, labels, sty, True)
+    tables, dtables = [], []
+    packed = ops.style_table_packed
+
+    def table_spy(*a, **kw):           # the per-image 32-column table the module builds, and the gradient its backward returns
+        t = packed(*a, **kw)
+        tables.append(t.detach())
+        if t.requires_grad:
+            t.register_hook(dtables.append)
+        return t
+
+    ops.style_table_packed = table_spy
+    try:
+        h = mod(xs, labels, sty, True)
+    finally:
+        ops.style_table_packed = packed
     h.backward(nhwc(gy))
     torch.cuda.synchronize()
     ft, gt = (1e-4, 5e-3) if wino else (TOL, 2e-4)
@@ -189,6 +233,21 @@ def test_sean_norm_table_path(kind, C, R, N, max_fm):
             assert p.grad is None or float(p.grad.abs().max()) == 0.0, k
         else:
             assert rel(p.grad.cpu(), ref) < gt, k
+    # exact zeros: columns >= Lc of the 32-column table and of its gradient; for a class that no pixel of the (resized) map of
+    # image b holds, its column of that image's table gradient, its row of the style gradient, and -- absent from every image --
+    # its slice of mlp_shared's weight gradient
+    low = label[:, 0, ::H // R, ::W // Rw].long()
+    gone = torch.stack([torch.bincount(im[im < Lc].reshape(-1), minlength=Lc) == 0 for im in low])
+    if kind != "spade" and not capped:
+        assert len(tables) == 1 and len(dtables) == 1 and tuple(dtables[0].shape) == (N, 9, tables[0].shape[2], 32)
+        assert Lc == 32 or (float(tables[0][..., Lc:].abs().sum()) == 0.0 and float(dtables[0][..., Lc:].abs().sum()) == 0.0)
+        dt = dtables[0].cpu()
+        for b in range(N):
+            assert float(dt[b][..., :Lc][..., gone[b]].abs().sum()) == 0.0, b
+        assert float(sty.grad.cpu()[gone].abs().sum()) == 0.0 and float(style.grad[gone].abs().sum()) == 0.0
+    if kind != "puresean":
+        assert float(dict(mod.named_parameters())["mlp_shared.0.weight"].grad.cpu()[:, gone.all(0)].abs().sum()) == 0.0
+    return gone
 
 
 @pytest.mark.parametrize("act", [1, 3])
@@ -901,14 +960,19 @@ def test_rccl_communicator_behind_the_c_abi_world1():
 
 @pytest.mark.parametrize("kind", ["sean", "spade"])
 def test_coarse_sean_norm_fwd_is_the_autograd_path(kind):
-    """dsee_sean_norm_fwd (include/deepsee_hip.h, coarse entry points): ONE C call = the whole SPADE / SEAN normalisation
+    coarse_sean_norm_fwd(kind)
+
+
+def coarse_sean_norm_fwd(kind, Lc=19):
+    """(The body, with the class count as an argument: tests/test_gpu_label_nc.py runs it at other counts than 19.)
+    dsee_sean_norm_fwd (include/deepsee_hip.h, coarse entry points): ONE C call = the whole SPADE / SEAN normalisation
     forward + LeakyReLU (embedding, batch statistics, operand transforms, fused gamma/beta kernel) from raw tensors in a
     caller-owned workspace -- what a host without deepsee_amd/ops.py would call.  Fed with the very tensors
     SeanNormTable.forward receives inside the module's forward, it must reproduce that forward bit for bit (h, the saved
     modulation factor, mean / invstd, the updated running statistics), training and evaluation mode."""
     import ctypes as C
     from deepsee_amd import ops, lib as L, networks as Nw
-    N, Cc, R, Lc, S, H = 2, 64, 64, 19, 128, 128      # (per-image tables: whole 128-tile GEMM tiles per image)
+    N, Cc, R, S, H = 2, 64, 64, 128, 128      # (per-image tables: whole 128-tile GEMM tiles per image)
     g = gen(77)
     label = F.interpolate(torch.randint(0, Lc, (N, 1, 8, 8), generator=g).float(), size=(H, H), mode="nearest")
     style = (torch.rand(N, Lc, S, generator=g) * 2 - 1).cuda()
@@ -966,7 +1030,13 @@ def test_coarse_sean_norm_fwd_is_the_autograd_path(kind):
 
 
 def test_coarse_spade_resblock_fwd_matches_the_module():
-    """dsee_spade_resblock_fwd: ONE C call = a whole SPADEResnetBlock forward (two SEAN norms on the fused kernel, two Winograd
+    coarse_spade_resblock_fwd()
+
+
+def coarse_spade_resblock_fwd(Lc=19, kind="sean"):
+    """(The body, with the class count and the block kind as arguments: tests/test_gpu_label_nc.py runs it at other counts than 19
+    and as a SPADE block, i.e. without style tables.)
+    dsee_spade_resblock_fwd: ONE C call = a whole SPADEResnetBlock forward (two SEAN norms on the fused kernel, two Winograd
     convolutions on pre-split operands, identity shortcut) from raw tensors and a caller-owned workspace -- against the Python
     module's forward (training mode, add_noise off) fed with the same effective weights.  Not bit-identical by construction:
     the module takes norm_1's batch statistics from the rows conv_0's output transform wrote and splits this small layer's V
@@ -975,10 +1045,10 @@ def test_coarse_spade_resblock_fwd_matches_the_module():
     import ctypes as C
     from deepsee_amd import ops, lib as L, networks as Nw
     from deepsee_amd.options import make_opt
-    N, Cc, R, Lc, S, H = 2, 256, 64, 19, 128, 128
+    N, Cc, R, S, H = 2, 256, 64, 128, 128
     g = gen(91)
-    opt = make_opt(ngf=Cc // 16, add_noise=False, start_size=8, crop_size=H, load_size=H, batchSize=N)
-    blk = Nw.SPADEResnetBlock(Cc, opt, "sean")
+    opt = make_opt(ngf=Cc // 16, add_noise=False, start_size=8, crop_size=H, load_size=H, batchSize=N, label_nc=Lc)
+    blk = Nw.SPADEResnetBlock(Cc, opt, kind)
     blk.load_state_dict({k: O.recipe_tensor("coarse_blk", k, v.shape, 1.0) for k, v in blk.state_dict().items()})
     blk.cuda()
     label = F.interpolate(torch.randint(0, Lc, (N, 1, 8, 8), generator=g).float(), size=(H, H), mode="nearest")
@@ -989,7 +1059,8 @@ def test_coarse_spade_resblock_fwd_matches_the_module():
     fwd, conv2d = ops.SeanNormTable._forward, ops.conv2d
 
     def norm_spy(ctx, x_, w_sh, b_sh, w2a, table, b2, rm, rv, labels_, shift, training_, add_one, grad_sink=None, cat_ups=0):
-        norms.append(dict(w_sh=w_sh.contiguous(), b_sh=b_sh.contiguous(), w2a=w2a.contiguous(), table=table.contiguous(),
+        norms.append(dict(w_sh=w_sh.contiguous(), b_sh=b_sh.contiguous(), w2a=w2a.contiguous(),
+                          table=None if table is None else table.contiguous(),
                           b2=b2.contiguous(), rm=rm.clone(), rv=rv.clone(), shift=shift, add_one=add_one))
         return fwd(ctx, x_, w_sh, b_sh, w2a, table, b2, rm, rv, labels_, shift, training_, add_one, grad_sink, cat_ups)
 
@@ -1010,10 +1081,13 @@ def test_coarse_spade_resblock_fwd_matches_the_module():
                                               "running_var")] + [("add_one", C.c_float)]
 
     def layer(d):
-        return NormLayer(d["w_sh"].data_ptr(), d["b_sh"].data_ptr(), d["w2a"].data_ptr(), d["table"].data_ptr(),
+        return NormLayer(d["w_sh"].data_ptr(), d["b_sh"].data_ptr(), d["w2a"].data_ptr(),
+                         None if d["table"] is None else d["table"].data_ptr(),
                          d["b2"].data_ptr(), d["rm"].data_ptr(), d["rv"].data_ptr(), float(d["add_one"]))
 
-    nbytes = L.lib().dsee_spade_resblock_fwd_workspace(N, R, R, Cc, Lc, 1)
+    has_t = norms[0]["table"] is not None
+    assert has_t == (kind == "sean") and has_t == (norms[1]["table"] is not None)
+    nbytes = L.lib().dsee_spade_resblock_fwd_workspace(N, R, R, Cc, Lc, int(has_t))
     ws = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
     out = torch.empty_like(x)
     n0, n1 = layer(norms[0]), layer(norms[1])
@@ -1034,7 +1108,12 @@ def test_coarse_spade_resblock_fwd_matches_the_module():
 
 @pytest.mark.parametrize("kind", ["sean", "spade"])
 def test_coarse_resblock_training_pair(kind):
-    """Round 6 (SURVEY 7 "whole resblock fwd/bwd"): dsee_spade_resblock_train_fwd + dsee_spade_resblock_bwd -- two C calls run the
+    coarse_resblock_training_pair(kind)
+
+
+def coarse_resblock_training_pair(kind, Lc=19):
+    """(The body, with the class count as an argument: tests/test_gpu_label_nc.py runs it at other counts than 19.)
+    Round 6 (SURVEY 7 "whole resblock fwd/bwd"): dsee_spade_resblock_train_fwd + dsee_spade_resblock_bwd -- two C calls run the
     hot block of configs[1] as it trains (architecture.py:75-147: two SPADE / SEAN norms on the fused kernel, two Winograd
     convolutions on pre-split operands, noise_middle in conv_0's output transform, the shortcut x + noise_skip(x) in conv_1's)
     forward AND backward, from raw tensors, a caller-owned `saved` area and workspaces -- against the Python module's own
@@ -1044,9 +1123,9 @@ def test_coarse_resblock_training_pair(kind):
     import ctypes as C
     from deepsee_amd import ops, lib as L, networks as Nw
     from deepsee_amd.options import make_opt
-    N, Cc, R, Lc, S, H = 8, 512, 64, 19, 128, 128
+    N, Cc, R, S, H = 8, 512, 64, 128, 128
     g = gen(17 + len(kind))
-    opt = make_opt(ngf=Cc // 16, add_noise=True, start_size=8, crop_size=H, load_size=H, batchSize=N)
+    opt = make_opt(ngf=Cc // 16, add_noise=True, start_size=8, crop_size=H, load_size=H, batchSize=N, label_nc=Lc)
     blk = Nw.SPADEResnetBlock(Cc, opt, kind)
     blk.load_state_dict({k: O.recipe_tensor("coarse_train_" + kind, k, v.shape, 1.0) for k, v in blk.state_dict().items()})
     blk.cuda()

@@ -20,6 +20,7 @@ import test_gpu_conv as TC
 import test_gpu_explore as TE
 import test_gpu_gan_mode as TG
 import test_gpu_instance_norm as TI
+import test_gpu_label_nc as TK
 import test_gpu_loader as TL
 import test_gpu_model as TM
 import test_gpu_ms_ssim as TS
@@ -200,6 +201,27 @@ S(TO.test_flat_adam_matches_torch_adam_incl_skipped_tensors_and_lr_change)
 S(TO.test_rng_statistics)
 S(TO.test_conv_noise_fused_in_output_transform_rect)
 S(TO.test_resblock_fused_noise_shortcut_and_gradient_sink, kind="spade", ups=1)
+
+# ---------------------------------------------------------------------------------------------- class counts 1 and 32
+# the two ends of the class count, where 9 L + 1 rows and slots x L x Cs floats size the workspaces, the LDS table of the one-hot
+# convolution is smallest / 144 KB, and the 32-column tables have no zero column: the smallest shape of each body
+for _l in (1, 32):
+    S(TK.test_onehot_conv3x3_fwd, shape="global_16x16", nl=_l, kind="uniform", co=128)
+    S(TK.test_onehot_conv3x3_fwd, shape="lds_46x46", nl=_l, kind="uniform", co=128)
+    S(TK.test_onehot_conv3x3_fwd, shape="lds4_64x64", nl=_l, kind="uniform", co=128)
+    S(TK.test_onehot_conv3x3_wgrad, shape="23x41", nl=_l, kind="uniform", ld=160)
+    S(TK.test_label_gather_and_segsum, shape="20x28", nl=_l, kind="uniform", cs=4)
+    S(TK.test_label_gather_and_segsum, shape="32x64s2", nl=_l, kind="uniform", cs=256)
+    S(TK.test_style_pool_fwd_bwd, nl=_l, kind="uniform")
+    S(TK.test_label_onehot, nl=_l, coff=128, pad=0)
+    S(TK.test_dinput_fwd_bwd, nl=_l)
+    S(TK.test_onehot_noise_conv3x3, shape=(2, 20, 40, _l, 32))
+    S(TK.test_style_table_layout_fwd_bwd, nl=_l)
+    S(TK.test_style_explore, nl=_l, flags=5)
+    S(TK.test_spade_sean_norm_direct_path, nl=_l, kind="uniform")
+    S(TK.test_sean_norm_table_path, nl=_l, kind="uniform", R=16)
+S(TK.test_onehot_conv3x3_fwd, shape="global_16x16", nl=32, kind="uniform", co=48)
+S(TK.test_onehot_noise_conv3x3_widest_at_32_classes)
 
 # ---------------------------------------------------------------------------------------------- metrics, visuals, loader, explore
 S(TO.test_psnr_ssim_rmse_kernel_matches_reference_numbers)
