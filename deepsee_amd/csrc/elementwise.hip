@@ -7,6 +7,7 @@
 //    (data/preprocessor.py:17-41, base_manager.py:28-66), discriminator input cat([seg, image]) (sr_model.py:655-668)
 //  * counter-based N(0,1)/U(0,1) generators (replaces tensor.normal_() / torch.rand_like on the device)
 #include "dsee_common.h"
+#include "dsee_interp.h"
 #include "dsee_rng.h"
 
 namespace {
@@ -330,17 +331,21 @@ __global__ void label_u8_prepare_kernel(const uint8_t* __restrict__ lab, const u
   }
 }
 
-// F.interpolate(mode='bicubic', align_corners=False) + clamp(-1,1); NHWC in (Cs_in) -> NHWC out (Cs_out), 3 channels
-__global__ void bicubic_down_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int S,
-                                    int cs_in, int cs_out) {
-  const long total = (long)N * S * S * cs_out;
-  const float sh = (float)H / S, sw = (float)W / S;
+// F.interpolate(x, (OH, OW), mode='bicubic', align_corners=False) [+ clamp(-1,1)]; NHWC in (Cs_in) -> NHWC out (Cs_out), 3
+// channels; one scale per axis, the same A = -0.75 formula down and up.  ONE kernel behind dsee_bicubic_down (OH = OW = S, clamp) and
+// the bicubic mode of dsee_resize_hw (dsee::launch_bicubic_hw): a square output of the latter has the bits of the former because it
+// is the same code object -- two copies of this arithmetic in two kernels need not be (the compiler contracts and vectorises the
+// tap sums differently from one context to the next, one ulp apart).
+__global__ void bicubic_hw_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W, int OH, int OW,
+                                  int cs_in, int cs_out, int clamp) {
+  const long total = (long)N * OH * OW * cs_out;
+  const float sh = (float)H / OH, sw = (float)W / OW;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const int c = (int)(i % cs_out);
     long t = i / cs_out;
-    const int ow = (int)(t % S);
-    t /= S;
-    const int oh = (int)(t % S), n = (int)(t / S);
+    const int ow = (int)(t % OW);
+    t /= OW;
+    const int oh = (int)(t % OH), n = (int)(t / OH);
     if (c >= 3) {
       y[i] = 0.f;
       continue;
@@ -360,7 +365,7 @@ __global__ void bicubic_down_kernel(const float* __restrict__ x, float* __restri
       }
       acc += wy[a] * row;
     }
-    y[i] = fminf(fmaxf(acc, -1.f), 1.f);
+    y[i] = clamp ? fminf(fmaxf(acc, -1.f), 1.f) : acc;
   }
 }
 
@@ -466,6 +471,14 @@ __global__ __launch_bounds__(256) void sumpool_dot_rng_kernel(const float* __res
 }
 
 }  // namespace
+
+// the launch of bicubic_hw_kernel, for dsee_bicubic_down (below) and dsee_resize_hw (resample.hip); the callers check the arguments
+int dsee::launch_bicubic_hw(const float* x, float* y, int N, int H, int W, int OH, int OW, int cs_in, int cs_out, int clamp,
+                            hipStream_t st) {
+  bicubic_hw_kernel<<<egrid((long)N * OH * OW * cs_out), 256, 0, st>>>(x, y, N, H, W, OH, OW, cs_in, cs_out, clamp);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
 
 extern "C" {
 
@@ -621,14 +634,19 @@ int dsee_avgpool3s2_bwd(const float* dy, float* dx, int N, int H, int W, int C, 
 }
 
 int dsee_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, hipStream_t st) {
-  DSEE_CHECK_ARG(x && y && C % 4 == 0 && H % 2 == 0 && W % 2 == 0);
+  // an odd H or W drops its last row / column, like nn.MaxPool2d(2, 2) (floor mode): the 5 x 4 map of VGG19 on a 40 x 32 image
+  DSEE_CHECK_ARG(x && y && C > 0 && C % 4 == 0 && N > 0 && H >= 2 && W >= 2);
   maxpool2_fwd_kernel<<<egrid((long)N * (H / 2) * (W / 2) * C / 4), 256, 0, st>>>(x, y, N, H, W, C);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }
 
 int dsee_maxpool2_bwd(const float* dy, const float* x, float* dx, int N, int H, int W, int C, hipStream_t st) {
-  DSEE_CHECK_ARG(dy && x && dx && C % 4 == 0 && H % 2 == 0 && W % 2 == 0);
+  DSEE_CHECK_ARG(dy && x && dx && C > 0 && C % 4 == 0 && N > 0 && H >= 2 && W >= 2);
+  if (H % 2 || W % 2) {      // the dropped last row / column belongs to no window: its gradient is zero
+    (void)hipMemsetAsync(dx, 0, (size_t)N * H * W * C * sizeof(float), st);
+    DSEE_LAUNCH_CHECK();
+  }
   maxpool2_bwd_kernel<<<egrid((long)N * (H / 2) * (W / 2) * C / 4), 256, 0, st>>>(dy, x, dx, N, H, W, C);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
@@ -694,9 +712,7 @@ int dsee_extract_image_grad(const float* din, float* dimg, long pixels, int L, i
 
 int dsee_bicubic_down(const float* x, float* y, int N, int H, int W, int S, int cs_in, int cs_out, hipStream_t st) {
   DSEE_CHECK_ARG(x && y && cs_in >= 3 && cs_out >= 3);
-  bicubic_down_kernel<<<egrid((long)N * S * S * cs_out), 256, 0, st>>>(x, y, N, H, W, S, cs_in, cs_out);
-  DSEE_LAUNCH_CHECK();
-  return DSEE_OK;
+  return dsee::launch_bicubic_hw(x, y, N, H, W, S, S, cs_in, cs_out, 1, st);
 }
 
 int dsee_rng_fill(float* out, long n, uint64_t seed, uint64_t offset, int normal, hipStream_t st) {

@@ -2,7 +2,10 @@
 //   dsee_resample_u8   Pillow's 8-bit separable resize (Image.resize with BICUBIC / BILINEAR / NEAREST on 'RGB' and 'L' images),
 //                      bit for bit, with the centre crop as a source box and the random crop as an output window
 //   dsee_interp_down   F.interpolate(hr, (S, S), mode = bilinear | nearest | area) + clamp(-1, 1)  (data/preprocessor.py:29-33)
+//   dsee_resize_hw     F.interpolate(x, (OH, OW), mode = bicubic | bilinear | nearest | area) [+ clamp(-1, 1)], down or up: the LR
+//                      image of a non-square batch (Preprocessor.downsample_image(hr, shape=(h, w))) and its bicubic 'baseline'
 #include "dsee_common.h"
+#include "dsee_interp.h"
 
 namespace {
 
@@ -75,18 +78,8 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
   }
 }
 
-enum { INTERP_BILINEAR = 0, INTERP_NEAREST = 1, INTERP_AREA = 2 };
-
-// source index and weight of the upper neighbour of ATen's upsample_bilinear2d (align_corners = False)
-__device__ __forceinline__ void bilinear_tap(float scale, int dst, int in, int& i0, int& i1, float& l1) {
-  const float s = fmaxf(scale * (dst + 0.5f) - 0.5f, 0.f);
-  i0 = min((int)s, in - 1);
-  i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
-}
-
 // NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3 channels (the rest of cs_out zero); sh = (float)H / S, sw = (float)W / S from the
-// host, so that the nearest index is the one ATen computes: min((int)floorf(dst * scale), in - 1)
+// host (dsee_interp.h: dsee_interp_px)
 __global__ __launch_bounds__(256) void interp_down_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W,
                                                           int S, int cs_in, int cs_out, int mode, float sh, float sw) {
   const long total = (long)N * S * S;
@@ -96,33 +89,27 @@ __global__ __launch_bounds__(256) void interp_down_kernel(const float* __restric
     const int oh = (int)(t % S), n = (int)(t / S);
     const float* img = x + (size_t)n * H * W * cs_in;
     float v[3] = {0.f, 0.f, 0.f};
-    if (mode == INTERP_NEAREST) {
-      const int iy = min((int)floorf(oh * sh), H - 1), ix = min((int)floorf(ow * sw), W - 1);
-      for (int c = 0; c < 3; ++c) v[c] = img[((size_t)iy * W + ix) * cs_in + c];
-    } else if (mode == INTERP_BILINEAR) {
-      int y0, y1, x0, x1;
-      float ly, lx;
-      bilinear_tap(sh, oh, H, y0, y1, ly);
-      bilinear_tap(sw, ow, W, x0, x1, lx);
-      for (int c = 0; c < 3; ++c) {
-        const float a = img[((size_t)y0 * W + x0) * cs_in + c], b = img[((size_t)y0 * W + x1) * cs_in + c];
-        const float d = img[((size_t)y1 * W + x0) * cs_in + c], e = img[((size_t)y1 * W + x1) * cs_in + c];
-        v[c] = (1.f - ly) * ((1.f - lx) * a + lx * b) + ly * ((1.f - lx) * d + lx * e);
-      }
-    } else {  // adaptive average: rows floor(i in / out) ... ceil((i + 1) in / out)
-      const int ya = (int)(((long)oh * H) / S), yb = (int)((((long)oh + 1) * H + S - 1) / S);
-      const int xa = (int)(((long)ow * W) / S), xb = (int)((((long)ow + 1) * W + S - 1) / S);
-      for (int yy = ya; yy < yb; ++yy) {
-        float row[3] = {0.f, 0.f, 0.f};
-        for (int xx = xa; xx < xb; ++xx)
-          for (int c = 0; c < 3; ++c) row[c] += img[((size_t)yy * W + xx) * cs_in + c];
-        for (int c = 0; c < 3; ++c) v[c] += row[c];
-      }
-      const float inv = (float)((yb - ya) * (xb - xa));
-      for (int c = 0; c < 3; ++c) v[c] /= inv;
-    }
+    dsee_interp_px(img, H, W, S, S, cs_in, mode, sh, sw, oh, ow, v);
     float* o = y + (size_t)i * cs_out;
     for (int c = 0; c < cs_out; ++c) o[c] = c < 3 ? fminf(fmaxf(v[c], -1.f), 1.f) : 0.f;
+  }
+}
+
+// NHWC [N][H][W][cs_in] -> [N][OH][OW][cs_out], one thread per output pixel, mode = bilinear | nearest | area: interp_down_kernel
+// with one output size per axis and an optional clamp (the same dsee_interp_px)
+__global__ __launch_bounds__(256) void resize_hw_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W,
+                                                        int OH, int OW, int cs_in, int cs_out, int mode, int clamp, float sh,
+                                                        float sw) {
+  const long total = (long)N * OH * OW;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int ow = (int)(i % OW);
+    const long t = i / OW;
+    const int oh = (int)(t % OH), n = (int)(t / OH);
+    const float* img = x + (size_t)n * H * W * cs_in;
+    float v[3] = {0.f, 0.f, 0.f};
+    dsee_interp_px(img, H, W, OH, OW, cs_in, mode, sh, sw, oh, ow, v);
+    float* o = y + (size_t)i * cs_out;
+    for (int c = 0; c < cs_out; ++c) o[c] = c < 3 ? (clamp ? fminf(fmaxf(v[c], -1.f), 1.f) : v[c]) : 0.f;
   }
 }
 
@@ -155,6 +142,18 @@ int dsee_interp_down(const float* x, float* y, int N, int H, int W, int S, int c
   DSEE_CHECK_ARG(mode == INTERP_BILINEAR || mode == INTERP_NEAREST || mode == INTERP_AREA);
   interp_down_kernel<<<rgrid((long)N * S * S), 256, 0, st>>>(x, y, N, H, W, S, cs_in, cs_out, mode, (float)H / (float)S,
                                                              (float)W / (float)S);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_resize_hw(const float* x, float* y, int N, int H, int W, int OH, int OW, int cs_in, int cs_out, int mode, int clamp,
+                   hipStream_t st) {
+  DSEE_CHECK_ARG(x && y && N > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && cs_in >= 3 && cs_out >= 3);
+  DSEE_CHECK_ARG(mode == INTERP_BILINEAR || mode == INTERP_NEAREST || mode == INTERP_AREA || mode == INTERP_BICUBIC);
+  DSEE_CHECK_ARG(clamp == 0 || clamp == 1);
+  if (mode == INTERP_BICUBIC) return dsee::launch_bicubic_hw(x, y, N, H, W, OH, OW, cs_in, cs_out, clamp, st);
+  resize_hw_kernel<<<rgrid((long)N * OH * OW), 256, 0, st>>>(x, y, N, H, W, OH, OW, cs_in, cs_out, mode, clamp,
+                                                             (float)H / (float)OH, (float)W / (float)OW);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }

@@ -384,6 +384,13 @@ class SpadeNorm(nn.Module):
         inside this norm's backward pass."""
         n, h, w, c = x.shape
         fm = h if self.kind == "spade" else min(h, self.max_fm)  # SPADE.forward has no fm cap
+        if h != w and self.kind != "spade":
+            # the cap of a non-square map is per axis in the reference (one nearest-neighbour factor each): not built here, and
+            # unreachable behind sr_model.check_geometry -- never decided from the height alone
+            if max(h, w) > self.max_fm:
+                raise ValueError("%s norm on a %d x %d map with max_fm_size=%d: the cap on non-square maps is not built"
+                                 % (self.kind, h, w, self.max_fm))
+            fm = h
         sh = self.mlp_shared._modules["0"]
         capped = fm != h
         if capped and (h * w) % 128 == 0 and c % 64 == 0:

@@ -217,15 +217,43 @@ def interp_down(img_nhwc, size, mode):
     return y
 
 
+RESIZE_MODES = dict(INTERP_MODES, bicubic=3)
+
+
+def resize_hw(img_nhwc, oh, ow, mode, clamp=True):
+    """dsee_resize_hw: F.interpolate(x, (oh, ow), mode)[.clamp(-1, 1)] for mode = bicubic | bilinear | nearest | area of a native image
+    [N,H,W,cs] -> [N,oh,ow,4], one scale per axis, down or up.  For oh == ow and clamp=True it has the bits of bicubic_down /
+    interp_down (the same device functions)."""
+    if mode not in RESIZE_MODES:
+        raise ValueError("resize_hw: mode must be one of %s, got %r" % (", ".join(RESIZE_MODES), mode))
+    n, h, w, cs = img_nhwc.shape
+    y = new(n, int(oh), int(ow), 4)
+    L.call("resize_hw", img_nhwc.contiguous(), y, n, h, w, int(oh), int(ow), cs, 4, RESIZE_MODES[mode], int(bool(clamp)))
+    y.dsee_layout = "nhwc"
+    return y
+
+
+def lr_shape(opt, H, W):
+    """(h, w) of the LR image of an H x W batch.  With f = crop_size // start_size a power of two that divides crop_size, H and W
+    exactly: (H // f, W // f) -- Preprocessor.downsample_image(hr, shape=(H / f, W / f)), the shape from which the generator's
+    upsampling levels arrive at H x W again.  Anything else (a loader mode whose shape depends on the file): the reference's
+    default, a start_size square.  Pure host arithmetic; never raises."""
+    s, crop = int(opt.start_size), int(opt.crop_size)
+    f = crop // s if s > 0 else 0
+    if f >= 1 and f & (f - 1) == 0 and s * f == crop and H % f == 0 and W % f == 0 and H >= f and W >= f:
+        return H // f, W // f
+    return s, s
+
+
 def lr_image(opt, hr_nhwc):
-    """The LR input of the generator: opt.downsampling_method selects the F.interpolate mode (preprocessor.py:29-30).  bicubic is
-    the kernel it has always been."""
+    """The LR input of the generator, lr_shape(opt, H, W) in size: opt.downsampling_method selects the F.interpolate mode
+    (preprocessor.py:29-30).  One kernel for every shape and mode (dsee_resize_hw); a square output has the bits of bicubic_down /
+    interp_down."""
     mode = getattr(opt, "downsampling_method", "bicubic")
-    if mode == "bicubic":
-        return bicubic_down(hr_nhwc, opt.start_size)
-    if mode not in INTERP_MODES:       # the reference's help text offers 'linear', which F.interpolate rejects for 4-D input
+    if mode not in RESIZE_MODES:       # the reference's help text offers 'linear', which F.interpolate rejects for 4-D input
         raise ValueError("downsampling_method must be one of bicubic, %s, got %r" % (", ".join(INTERP_MODES), mode))
-    return interp_down(hr_nhwc, opt.start_size, mode)
+    oh, ow = lr_shape(opt, hr_nhwc.shape[1], hr_nhwc.shape[2])
+    return resize_hw(hr_nhwc, oh, ow, mode, clamp=True)
 
 
 def resample_u8(src, tables, out_wh, box=None):

@@ -40,6 +40,27 @@ def block_plan(opt):
     return plan + [("up_list.%d" % i, k) for i, k in enumerate(kinds)]
 
 
+def check_geometry(opt, plan, lr_h, lr_w):
+    """Refuse, on the host and before any launch, an LR shape the generator cannot run.  `plan` is block_plan(opt); the levels
+    are (lr_h << l, lr_w << l): head_0 at l = 0, G_middle_0 / G_middle_1 at 1, up_list.i at 2 + i.  A SEAN or PureSEAN level of
+    a NON-SQUARE map larger than opt.max_fm_size on either axis raises ValueError: the reference squashes such a map to
+    [min(h, cap), min(w, cap)] with one nearest-neighbour factor per axis (normalization.py:172-174, 188-190), and the label
+    kernels here index row h << shift, column w << shift with ONE shift.  That path is not built: set max_fm_size >= the long
+    side.  Square maps keep the reference's cap."""
+    lr_h, lr_w = int(lr_h), int(lr_w)
+    if lr_h < 1 or lr_w < 1:
+        raise ValueError("LR image of %d x %d" % (lr_h, lr_w))
+    level = 0
+    for i, (name, kind) in enumerate(plan):
+        if i == 1 or i >= 3:          # G_middle_0 and every up_list block upsample their input by 2
+            level += 1
+        h, w = lr_h << level, lr_w << level
+        if kind in ("sean", "puresean") and h != w and max(h, w) > opt.max_fm_size:
+            raise ValueError("generator level %d (%s, %s): the %d x %d map is not square and exceeds max_fm_size=%d; the per-axis "
+                             "cap of the reference is not built for non-square maps -- set max_fm_size >= %d"
+                             % (level, name, kind, h, w, opt.max_fm_size, max(lr_h, lr_w) << max(len(plan) - 2, 1)))
+
+
 def init_weights(net, init_type, gain, gen):
     """base_network.py:28-59 semantics on our parameter holders: xavier_normal(gain) (or kaiming / normal) on
     every conv weight incl. spectral-norm weight_orig and the unused Conv1d; biases 0; noise weights 0;
@@ -110,7 +131,8 @@ class SRModel(nn.Module):
         self.use_E = opt.netE is not None and len(opt.netE) > 0
         self.model_variant = "guided" if (self.use_E and "full" in opt.netE) else "independent"   # sr_model.py:26-30
         gen = torch.Generator().manual_seed(int(getattr(opt, "seed", 0)))
-        self.netSR = N.DeepSEESR(opt, block_plan(opt))
+        self._block_plan = block_plan(opt)
+        self.netSR = N.DeepSEESR(opt, self._block_plan)
         init_weights(self.netSR, opt.init_type, opt.init_variance, gen)
         self.netD = None
         self.gan_modes = None
@@ -158,6 +180,12 @@ class SRModel(nn.Module):
             return self._forward(data, mode, **kwargs)
 
     def _forward(self, data, mode, **kwargs):
+        if mode in ("generator", "discriminator", "inference", "demo") or mode in explore.MODES:
+            # every mode that runs the generator: the LR shape is checked on the host before the first kernel of this forward
+            lr = data.get("image_lr")
+            if isinstance(lr, torch.Tensor) and lr.dim() == 4:
+                hw = lr.shape[1:3] if getattr(lr, "dsee_layout", None) == "nhwc" else lr.shape[2:4]
+                check_geometry(self.opt, self._block_plan, hw[0], hw[1])
         d = self._native(data)
         if mode in ("generator", "discriminator"):
             self.noise.begin_step()     # fresh Philox positions / branch coins for this forward
@@ -189,8 +217,11 @@ class SRModel(nn.Module):
             return {k: v for k, v in data.items() if v is not None}
         elif mode == "baseline":
             # sr_model.py:109-115: bicubic upsampling of the LR image to the HR size, clamped -- no network, no noise, no coins
-            hr = d["image_hr"]
-            up = ops.bicubic_up(d["image_lr"], hr.shape[1], hr.shape[2], clamp=True)
+            hr, lr = d["image_hr"], d["image_lr"]
+            if lr.shape[1] == lr.shape[2]:
+                up = ops.bicubic_up(lr, hr.shape[1], hr.shape[2], clamp=True)
+            else:       # a non-square LR image: the same A = -0.75 formula with one scale per axis (dsee_resize_hw)
+                up = ops.resize_hw(lr, hr.shape[1], hr.shape[2], "bicubic", clamp=True)
             return OrderedDict([("input_label", data.get("input_semantics")), ("image_downsized", data.get("image_lr")),
                                 ("fake_image", ops.to_nchw(up, 3)), ("image_full", data.get("image_hr"))])
         elif mode in explore.MODES:

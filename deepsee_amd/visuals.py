@@ -15,8 +15,10 @@ files will take them from, and 3 bytes per pixel leave the card.
     buffers, and one host thread encodes the PNGs with PIL and writes them while the device works on the next batch.
 
 The LR column of the combined strip is the one piece that is not pinned to the reference: it resizes with cv2 there; here it is
-the bilinear upsampling dsee_bilinear_up_u8 defines (half-pixel centres, clamped borders, fp32, rounded half up).  The label
-columns need no resize: the label map is kept at the HR size.
+the bilinear upsampling dsee_bilinear_up_u8 defines (half-pixel centres, clamped borders, fp32, rounded half up).  That entry
+point takes one source side; a non-square LR image (a non-square batch, ops.lr_shape) is upsampled by dsee_resize_hw (the same
+half-pixel bilinear on the fp32 image) and converted by dsee_image_to_u8 like every other column.  The label columns need no
+resize: the label map is kept at the HR size.
 """
 import os
 import queue
@@ -229,13 +231,15 @@ class _Layout:
         native = getattr(hr, "dsee_layout", None) == "nhwc"
         self.n = hr.shape[0]
         self.h, self.w = (hr.shape[1], hr.shape[2]) if native else (hr.shape[2], hr.shape[3])
-        self.s = visuals["image_lr"].shape[2]
+        lr = visuals["image_lr"]
+        self.sh, self.sw = (lr.shape[1], lr.shape[2]) if getattr(lr, "dsee_layout", None) == "nhwc" else (lr.shape[2], lr.shape[3])
+        self.s = self.sw        # (the side of a square LR image, what dsee_bilinear_up_u8 takes)
         self.guided = "guiding_image" in visuals
         self.keys = SAVE_KEYS + (GUIDED_KEYS if self.guided else ())
         self.columns = len(self.keys)
         self.region, off = OrderedDict(), 0
         for k in self.keys:
-            h, w = (self.s, self.s) if k == "image_lr" else (self.h, self.w)
+            h, w = (self.sh, self.sw) if k == "image_lr" else (self.h, self.w)
             self.region[k] = (off, h, w)
             off = _align(off + self.n * h * w * 3)
         self.region["combined"] = (off, self.h, self.columns * self.w)
@@ -275,8 +279,16 @@ def render(visuals, arena, layout):
             for win in targets:
                 label_colorize(lab, n_label, win)
         elif key == "image_lr":
-            image_to_u8(_device_image(visuals[key]), targets[0])
-            bilinear_up_u8(targets[0], layout.n, layout.s, targets[1], layout.h, layout.w)
+            lr = _device_image(visuals[key])
+            image_to_u8(lr, targets[0])
+            if layout.sh == layout.sw:
+                bilinear_up_u8(targets[0], layout.n, layout.s, targets[1], layout.h, layout.w)
+            else:
+                # dsee_bilinear_up_u8 takes ONE source side.  A non-square LR image is upsampled in fp32 (dsee_resize_hw, the
+                # same half-pixel bilinear, no clamp needed: a convex combination) and converted like every other column
+                if getattr(lr, "dsee_layout", None) != "nhwc":
+                    lr = ops.to_nhwc(lr)
+                image_to_u8(ops.resize_hw(lr, layout.h, layout.w, "bilinear", clamp=False), targets[1])
         else:
             img = _device_image(visuals[key])
             for win in targets:

@@ -701,7 +701,8 @@ int dsee_axpby(const float* a, float alpha, const float* b, float beta, float* y
 /* F.avg_pool2d(3, stride 2, pad 1, count_include_pad=False)  (discriminator.py:46-49) */
 int dsee_avgpool3s2_fwd(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream);
 int dsee_avgpool3s2_bwd(const float* dy, float* dx, int N, int H, int W, int C, hipStream_t stream);
-/* VGG19 MaxPool2d(2,2) (architecture.py:151-181) */
+/* VGG19 MaxPool2d(2,2) (architecture.py:151-181): [N][H][W][C] -> [N][H/2][W/2][C]; an odd H or W drops its last row / column
+ * (floor mode) and the backward pass writes zeros there.  H, W >= 2, C % 4 == 0. */
 int dsee_maxpool2_fwd(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream);
 int dsee_maxpool2_bwd(const float* dy, const float* x, float* dx, int N, int H, int W, int C, hipStream_t stream);
 /* input preparation (base_manager.py:28-66, data/preprocessor.py:17-41) */
@@ -736,6 +737,13 @@ int dsee_resample_u8(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int N, int 
  * over floor(i in / out) ... ceil((i + 1) in / out)).  NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3 channels, like
  * dsee_bicubic_down: the source may be rectangular. */
 int dsee_interp_down(const float* x, float* y, int N, int H, int W, int S, int cs_in, int cs_out, int mode, hipStream_t stream);
+/* F.interpolate(x, (OH, OW), mode)[.clamp(-1, 1)] with one scale per axis (H / OH, W / OW), down- or up-sampling: mode 0 = bilinear,
+ * 1 = nearest, 2 = area as in dsee_interp_down, 3 = bicubic (A = -0.75, align_corners=False, border indices clamped, the same formula
+ * in both directions); clamp = 1 clamps to [-1, 1].  NHWC [N][H][W][cs_in] -> [N][OH][OW][cs_out], 3 channels, the rest of cs_out
+ * zero.  It runs the device functions of dsee_bicubic_down / dsee_interp_down: for OH == OW and clamp = 1 the result has their bits.
+ * The LR image of a rectangular batch (Preprocessor.downsample_image(hr, shape=(h, w))) and its bicubic `baseline`. */
+int dsee_resize_hw(const float* x, float* y, int N, int H, int W, int OH, int OW, int cs_in, int cs_out, int mode, int clamp,
+                   hipStream_t stream);
 /* cat([input_semantics, image], dim=1) of sr_model.py:655-668 in NHWC, and the image part of its gradient */
 int dsee_build_d_input(const uint8_t* lab, const float* img, float* out, long pixels, int L, int Cs, int img_cs,
                        hipStream_t stream);
