@@ -18,9 +18,17 @@ and yields {'image_raw': uint8 [Hs,Ws,3], 'label_raw': uint8 [Hl,Wl], 'crop_pos'
 are uploaded as they are and dsee_resample_u8 does the centre crop, the resize (Pillow's 8-bit arithmetic, bit for bit) and the
 random crop on the device, which gives the wire format above.  The tables that drive it come from deepsee_amd/resample.py.
 DeviceLoader(workers=k) decodes the samples of a batch on k threads (PIL releases the GIL while it decodes).
+
+Guided variant (opt.guiding_style_image): FolderDataset and RawFolderDataset add a second file of the same identity to every
+item ('guiding_label' / 'guiding_image', resp. 'guiding_label_raw' / 'guiding_image_raw' + 'guiding_path'), chosen through an
+IdentityIndex (the identities file of CelebAMask-HQ or CelebA) by the rules of DESIGN 4.3; the guide shares the sample's crop
+position and flip and, where the files have one size, its dsee_resample_u8 launches.  create_dataloader(opt) builds the loader
+from the reference's option names (data/__init__.py:41-54).
 """
+import csv
 import os
 import random
+import re
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -63,13 +71,132 @@ class SyntheticDataset:
         return out
 
 
-class FolderDataset:
+class SkipSampleException(ValueError):
+    """A sample that cannot be served (data/custom_exception.py): no guide is left for it.  A ValueError, because that is what
+    the reference's CelebAMask-HQ path ends in there (random.sample of an empty set) and what InferenceManager.run skips on."""
+
+
+DATASET_MODES = ("celebamaskhq", "celeba")
+
+
+def _stem(path):
+    return os.path.splitext(os.path.basename(path))[0]
+
+
+class IdentityIndex:
+    """file id <-> identity, from an identities file of either dataset:
+    *.csv       CelebAMask-HQ, as celebamaskhq_compute_identities_file.py:69-70 writes it (every field quoted): an index
+                column, then hq_file_id, celeba_file_id, identity, count;
+    otherwise   CelebA: one '<filename> <identity>' line per file, id = the filename without its extension."""
+
+    def __init__(self, id2identity, path=""):
+        self.path = path
+        self.id2identity = dict(id2identity)
+        self.identity2ids = {}
+        for file_id, identity in self.id2identity.items():
+            self.identity2ids.setdefault(identity, set()).add(file_id)
+
+    @classmethod
+    def from_file(cls, path):
+        path = str(path)
+        id2identity = {}
+        if path.lower().endswith(".csv"):
+            with open(path, newline="") as f:
+                rows = csv.reader(f)
+                header = next(rows)
+                try:
+                    fid, ident = header.index("hq_file_id"), header.index("identity")
+                except ValueError:
+                    raise ValueError("%s: no hq_file_id / identity column in %r" % (path, header))
+                for row in rows:
+                    if row:
+                        id2identity[row[fid]] = row[ident]
+        else:
+            with open(path) as f:
+                for line in f:
+                    if line.strip():
+                        filename, identity = line.split()
+                        id2identity[os.path.splitext(filename)[0]] = identity
+        return cls(id2identity, path)
+
+    def __len__(self):
+        return len(self.id2identity)
+
+    def __eq__(self, other):
+        return isinstance(other, IdentityIndex) and self.id2identity == other.id2identity
+
+    def restrict(self, file_ids):
+        """The index of these file ids alone (celebamaskhq_dataset.py:25-27: the rows of the data set's split)."""
+        keep = set(file_ids)
+        return IdentityIndex({k: v for k, v in self.id2identity.items() if k in keep}, self.path)
+
+    def candidates(self, file_id, exclude_self):
+        """The ids of file_id's identity, sorted as strings; without file_id itself if exclude_self."""
+        if file_id not in self.id2identity:
+            raise KeyError("file id %r has no entry in the identities file %s" % (file_id, self.path))
+        ids = self.identity2ids[self.id2identity[file_id]]
+        return sorted(k for k in ids if not (exclude_self and k == file_id))
+
+
+class _FilePairs:
+    """What FolderDataset and RawFolderDataset share: the file pairs, and the guide of an item (a second file of the same person,
+    base_dataset.py:118-140 + sample_guiding_image of celebamaskhq_dataset.py / celeba_dataset.py)."""
+
+    def _init_files(self, opt, label_dir, image_dir, identities, dataset_mode, order, max_dataset_size):
+        if dataset_mode not in DATASET_MODES:
+            raise ValueError("dataset_mode must be one of %s, got %r" % (", ".join(DATASET_MODES), dataset_mode))
+        pairs = _paired_files(label_dir, image_dir, order)
+        self.items = pairs if max_dataset_size is None else pairs[:max_dataset_size]
+        self.dataset_mode, self.identities = dataset_mode, None
+        if not getattr(opt, "guiding_style_image", False):
+            return
+        if identities is None:
+            identities = getattr(opt, "identities_file", "")
+        assert identities, "Please provide an identity file."
+        if not isinstance(identities, IdentityIndex):
+            assert os.path.exists(identities), \
+                "Please provide a correct path to the identities file (invalid path: {})".format(identities)
+            identities = IdentityIndex.from_file(identities)
+        # CelebAMask-HQ: the rows of this data set (after max_dataset_size, like the reference).  CelebA: the reference does not
+        # filter; the ids of the folder, which only removes candidates whose file it would fail to open (DESIGN 4.3).
+        self.by_id = {_stem(ip): (lp, ip) for lp, ip in (self.items if dataset_mode == "celebamaskhq" else pairs)}
+        self.identities = identities.restrict(self.by_id)
+        phase = getattr(opt, "phase", "train")
+        self.exclude_self = phase != "train" if dataset_mode == "celebamaskhq" else phase == "test"
+
+    def guide_candidates(self, i):
+        file_id = _stem(self.items[i][1])
+        cands = self.identities.candidates(file_id, self.exclude_self)
+        if not cands:
+            raise SkipSampleException("There is no other candidate for file id: {}".format(file_id))
+        return cands
+
+    def _guide(self, cands, rng):
+        """(label path, image path) of the guide: one draw, made after the three of the crop position and the flip."""
+        return self.by_id[cands[rng.randrange(len(cands))]]
+
+    def __len__(self):
+        return len(self.items)
+
+
+def _open_label(path):
+    from PIL import Image
+    lab = Image.open(path)
+    if lab.mode not in ("L", "P"):
+        raise ValueError("%s: label maps are single-channel class-index images, got mode %r" % (path, lab.mode))
+    return lab
+
+
+class FolderDataset(_FilePairs):
     """label_dir/<id>.png (uint8 class indices, 255 = unknown) + image_dir/<id>.jpg pairs, matched by file stem like
     base_dataset.py:44-62 (paths_match).  'resize_and_crop': both are resized to load_size (NEAREST for the label,
     BICUBIC for the image, base_dataset.py:92,107), cropped to crop_size at one random position and flipped with
-    p = 0.5 in training (the flip itself happens on the device)."""
+    p = 0.5 in training (the flip itself happens on the device).  With opt.guiding_style_image the item also holds
+    'guiding_label' / 'guiding_image': a file of the same identity (`identities`: an IdentityIndex or the path of an identities
+    file, default opt.identities_file), drawn after the flip, resized and cropped with the sample's box."""
 
-    def __init__(self, opt, label_dir, image_dir, seed=0, no_flip=None):
+    def __init__(self, opt, label_dir, image_dir, seed=0, no_flip=None, identities=None, dataset_mode="celebamaskhq",
+                 order="stem", max_dataset_size=None):
         from PIL import Image  # noqa: F401  (fail here, not in a worker)
         mode = getattr(opt, "preprocess_mode", "resize_and_crop")
         if mode != "resize_and_crop":     # (base_dataset.py:76-104 also knows scale_width*, fixed, none: not restated here)
@@ -77,78 +204,90 @@ class FolderDataset:
         self.opt = opt
         self.no_flip = bool(getattr(opt, "no_flip", False)) if no_flip is None else bool(no_flip)
         self.rng = random.Random(seed)
-        labels = {os.path.splitext(f)[0]: os.path.join(label_dir, f) for f in sorted(os.listdir(label_dir))
-                  if f.lower().endswith(IMG_EXT)}
-        images = {os.path.splitext(f)[0]: os.path.join(image_dir, f) for f in sorted(os.listdir(image_dir))
-                  if f.lower().endswith(IMG_EXT)}
-        missing = sorted(set(labels) ^ set(images))
-        assert not missing, "label/image files without a partner (first: %s)" % missing[:3]
-        self.items = [(labels[k], images[k]) for k in sorted(labels)]
-
-    def __len__(self):
-        return len(self.items)
+        self._init_files(opt, label_dir, image_dir, identities, dataset_mode, order, max_dataset_size)
 
     def __getitem__(self, i):
         from PIL import Image
         opt = self.opt
         lp, ip = self.items[i]
+        cands = self.guide_candidates(i) if self.identities is not None else None    # (skips before anything is drawn)
         x = self.rng.randint(0, max(0, opt.load_size - opt.crop_size))
         y = self.rng.randint(0, max(0, opt.load_size - opt.crop_size))
         flip = int(self.rng.random() > 0.5) if (opt.isTrain and not self.no_flip) else 0
+        if cands is not None and not (opt.isTrain and not self.no_flip):
+            self.rng.random()      # get_params draws the flip whether it is used or not: the guide's draw is always the fourth
         box = (x, y, x + opt.crop_size, y + opt.crop_size)
-        lab = Image.open(lp)
-        if lab.mode not in ("L", "P"):
-            raise ValueError("%s: label maps are single-channel class-index images, got mode %r" % (lp, lab.mode))
-        lab = lab.resize((opt.load_size, opt.load_size), Image.NEAREST).crop(box)
-        img = Image.open(ip).convert("RGB").resize((opt.load_size, opt.load_size), Image.BICUBIC).crop(box)
-        return {"label": np.asarray(lab, dtype=np.uint8), "image": np.asarray(img, dtype=np.uint8), "flip": flip,
-                "path": ip}
+
+        def load(lp, ip):
+            lab = _open_label(lp).resize((opt.load_size, opt.load_size), Image.NEAREST).crop(box)
+            img = Image.open(ip).convert("RGB").resize((opt.load_size, opt.load_size), Image.BICUBIC).crop(box)
+            return np.asarray(lab, dtype=np.uint8), np.asarray(img, dtype=np.uint8)
+
+        lab, img = load(lp, ip)
+        out = {"label": lab, "image": img, "flip": flip, "path": ip}
+        if cands is not None:
+            out["guiding_label"], out["guiding_image"] = load(*self._guide(cands, self.rng))
+        return out
 
 
-class RawFolderDataset:
+class RawFolderDataset(_FilePairs):
     """The file pairs of FolderDataset, decoded and nothing else: every preprocess_mode is accepted, because the geometry runs on
     the device (device_preprocess).  Image and label file may differ in size (1024^2 and 512^2 in CelebAMask-HQ); the crop
-    position is drawn for the LABEL file's size and applied to both, like base_dataset.py:91-106.  Crop position and flip are a
-    pure function of (seed, epoch, index) -- set_epoch(e) is called by DeviceLoader at each __iter__ -- so items do not depend
-    on the order, or the thread, in which they are loaded."""
+    position is drawn for the LABEL file's size and applied to both, like base_dataset.py:91-106.  Crop position, flip and guide
+    are a pure function of (seed, epoch, index) -- set_epoch(e) is called by DeviceLoader at each __iter__ -- so items do not
+    depend on the order, or the thread, in which they are loaded.  With opt.guiding_style_image the item also holds
+    'guiding_label_raw', 'guiding_image_raw' and 'guiding_path' (see FolderDataset); the guide shares the sample's crop_pos."""
     thread_safe = True
 
-    def __init__(self, opt, label_dir, image_dir, seed=0, no_flip=None):
+    def __init__(self, opt, label_dir, image_dir, seed=0, no_flip=None, identities=None, dataset_mode="celebamaskhq",
+                 order="stem", max_dataset_size=None):
         from PIL import Image  # noqa: F401  (fail here, not in a worker)
         mode = getattr(opt, "preprocess_mode", "resize_and_crop")
         if mode not in R.MODES:
             raise ValueError("preprocess_mode must be one of %s, got %r" % (", ".join(R.MODES), mode))
         self.opt, self.seed, self.epoch = opt, int(seed), 0
         self.no_flip = bool(getattr(opt, "no_flip", False)) if no_flip is None else bool(no_flip)
-        self.items = _paired_files(label_dir, image_dir)
+        self._init_files(opt, label_dir, image_dir, identities, dataset_mode, order, max_dataset_size)
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
 
-    def __len__(self):
-        return len(self.items)
-
     def __getitem__(self, i):
         from PIL import Image
         lp, ip = self.items[i]
-        lab = Image.open(lp)
-        if lab.mode not in ("L", "P"):
-            raise ValueError("%s: label maps are single-channel class-index images, got mode %r" % (lp, lab.mode))
-        params = R.crop_params(self.opt, lab.size, random.Random((self.seed * 1000003 + self.epoch) * 1000003 + int(i)))
+        cands = self.guide_candidates(i) if self.identities is not None else None    # (skips before anything is decoded)
+        lab = _open_label(lp)
+        rng = random.Random((self.seed * 1000003 + self.epoch) * 1000003 + int(i))
+        params = R.crop_params(self.opt, lab.size, rng)
         flip = int(params["flip"]) if (self.opt.isTrain and not self.no_flip) else 0
-        return {"label_raw": np.asarray(lab, dtype=np.uint8), "image_raw": np.asarray(Image.open(ip).convert("RGB"), dtype=np.uint8),
-                "crop_pos": params["crop_pos"], "flip": flip, "path": ip}
+        out = {"label_raw": np.asarray(lab, dtype=np.uint8), "image_raw": np.asarray(Image.open(ip).convert("RGB"), dtype=np.uint8),
+               "crop_pos": params["crop_pos"], "flip": flip, "path": ip}
+        if cands is not None:
+            glp, gip = self._guide(cands, rng)
+            out["guiding_label_raw"] = np.asarray(_open_label(glp), dtype=np.uint8)
+            out["guiding_image_raw"] = np.asarray(Image.open(gip).convert("RGB"), dtype=np.uint8)
+            out["guiding_path"] = gip
+        return out
 
 
-def _paired_files(label_dir, image_dir):
-    """[(label path, image path)] matched by file stem (base_dataset.py:44-62, paths_match), sorted by stem."""
+def _natural_key(text):
+    """util/util.py:174-184 (natural_keys): digit runs compare as numbers, so 2.png sorts before 10.png."""
+    return [int(c) if c.isdigit() else c for c in re.split(r"(\d+)", text)]
+
+
+def _paired_files(label_dir, image_dir, order="stem"):
+    """[(label path, image path)] matched by file stem (base_dataset.py:44-62, paths_match).  order: 'stem' (sorted by stem) or
+    'natural' (the label files' names in the reference's natural sort, base_dataset.py:51-52)."""
+    if order not in ("stem", "natural"):
+        raise ValueError("order must be 'stem' or 'natural', got %r" % (order,))
     labels = {os.path.splitext(f)[0]: os.path.join(label_dir, f) for f in sorted(os.listdir(label_dir))
               if f.lower().endswith(IMG_EXT)}
     images = {os.path.splitext(f)[0]: os.path.join(image_dir, f) for f in sorted(os.listdir(image_dir))
               if f.lower().endswith(IMG_EXT)}
     missing = sorted(set(labels) ^ set(images))
     assert not missing, "label/image files without a partner (first: %s)" % missing[:3]
-    return [(labels[k], images[k]) for k in sorted(labels)]
+    stems = sorted(labels) if order == "stem" else sorted(labels, key=lambda k: _natural_key(os.path.basename(labels[k])))
+    return [(labels[k], images[k]) for k in stems]
 
 
 def stack_raw(arrays, paths=None):
@@ -164,13 +303,14 @@ def stack_raw(arrays, paths=None):
     return torch.from_numpy(np.stack([np.asarray(a, dtype=np.uint8) for a in arrays]))
 
 
-def resample_raw(opt, raw, crop_pos, filt):
+def resample_raw(opt, raw, crop_pos, filt, mode=None):
     """Load-time geometry of a raw uint8 batch [N,Hs,Ws(,3)] on the device: centre crop, resize and crop of opt.preprocess_mode
-    (resample.load_geometry) through dsee_resample_u8 with `filt` -> uint8 [N,H,W(,3)], the wire format."""
+    (resample.load_geometry; `mode` instead, where given) through dsee_resample_u8 with `filt` -> uint8 [N,H,W(,3)], the wire
+    format."""
     raw = raw if raw.is_cuda else raw.cuda(non_blocking=True)
     n, hs, ws = raw.shape[:3]
     assert len(crop_pos) == n, "one crop position per sample"
-    geos = [R.load_geometry(opt, (ws, hs), tuple(int(v) for v in p)) for p in crop_pos]
+    geos = [R.load_geometry(opt, (ws, hs), tuple(int(v) for v in p), mode) for p in crop_pos]
     tab = R.batch_tables(geos, filt)
     flat = torch.from_numpy(np.concatenate([tab[k].reshape(-1) for k in ("xtab", "ytab", "rows")])).cuda(non_blocking=True)
     dev, at = {"tmp_rows": tab["tmp_rows"]}, 0
@@ -185,18 +325,36 @@ def device_preprocess(opt, batch, stream=None):
     batch: 'label' uint8 [N,H,W], 'image' uint8 [N,H,W,3], optional 'flip' uint8 [N], 'guiding_*', 'path' -- or the raw form
     'label_raw' uint8 [N,Hl,Wl], 'image_raw' uint8 [N,Hs,Ws,3] (tensors, or lists of arrays of one size) + 'crop_pos' [N] of
     (x, y), which dsee_resample_u8 turns into the former: the image with Pillow's BILINEAR if opt.downsampling_method is
-    'bilinear' and BICUBIC otherwise (base_dataset.py:45-47), the label with NEAREST."""
+    'bilinear' and BICUBIC otherwise (base_dataset.py:45-47), the label with NEAREST and the geometry of
+    opt.label_preprocess_mode (None: opt.preprocess_mode, like the image).  'guiding_label_raw' / 'guiding_image_raw' share the
+    samples' crop positions; where they also share their sizes, samples and guides go through dsee_resample_u8 as one batch of
+    2N (one call for the images, one for the label maps), otherwise through calls of their own."""
     def dev(t):
         return t if t.is_cuda else t.cuda(non_blocking=True)
 
     if "image_raw" in batch:
         filt = R.BILINEAR if getattr(opt, "downsampling_method", "bicubic") == "bilinear" else R.BICUBIC
-        wire, paths = dict(batch), batch.get("path")
-        for pre in ("", "guiding_"):
-            if pre + "image_raw" not in batch:
-                continue
-            img = resample_raw(opt, stack_raw(batch[pre + "image_raw"], paths), batch["crop_pos"], filt)
-            lab = resample_raw(opt, stack_raw(batch[pre + "label_raw"], paths), batch["crop_pos"], R.NEAREST)
+        lmode = getattr(opt, "label_preprocess_mode", None)        # celeba_dataset.py:53-55: 'resize' for the label maps
+        wire, pos = dict(batch), list(batch["crop_pos"])
+        raws = {pre: (stack_raw(batch[pre + "image_raw"], batch.get(pre + "path", batch.get("path"))),
+                      stack_raw(batch[pre + "label_raw"], batch.get(pre + "path", batch.get("path"))))
+                for pre in ("", "guiding_") if pre + "image_raw" in batch}
+        n = len(pos)
+
+        def both(a, b):                      # samples and guides of one size: one device batch of 2N, uploaded in place
+            out = torch.empty((2 * n,) + tuple(a.shape[1:]), dtype=torch.uint8, device="cuda")
+            out[:n].copy_(a, non_blocking=True)
+            out[n:].copy_(b, non_blocking=True)
+            return out
+
+        if len(raws) == 2 and all(raws[""][k].shape == raws["guiding_"][k].shape and raws[""][k].shape[0] == n for k in (0, 1)):
+            img = resample_raw(opt, both(raws[""][0], raws["guiding_"][0]), pos * 2, filt)
+            lab = resample_raw(opt, both(raws[""][1], raws["guiding_"][1]), pos * 2, R.NEAREST, lmode)
+            done = {"": (img[:n], lab[:n]), "guiding_": (img[n:], lab[n:])}
+        else:
+            done = {pre: (resample_raw(opt, img, pos, filt), resample_raw(opt, lab, pos, R.NEAREST, lmode))
+                    for pre, (img, lab) in raws.items()}
+        for pre, (img, lab) in done.items():
             if img.shape[1:3] != lab.shape[1:3]:
                 raise ValueError("preprocess_mode=%r leaves the image at %s and the label map at %s"
                                  % (opt.preprocess_mode, tuple(img.shape[1:3]), tuple(lab.shape[1:3])))
@@ -225,8 +383,9 @@ def device_preprocess(opt, batch, stream=None):
     if "guiding_image" in batch:
         res["guiding_image"] = image(batch["guiding_image"])
         res["guiding_label"] = labels(batch["guiding_label"])
-    if "path" in batch:
-        res["path"] = batch["path"]
+    for key in ("path", "guiding_path"):
+        if key in batch:
+            res[key] = batch[key]
     return res
 
 
@@ -274,8 +433,12 @@ class DeviceLoader:
         if pin:
             out["flip"] = out["flip"].pin_memory()
         if "image_raw" in samples[0]:
-            for key in ("label_raw", "image_raw"):
-                t = stack_raw([s[key] for s in samples], out["path"])
+            keys = [("label_raw", "path"), ("image_raw", "path")]
+            if "guiding_image_raw" in samples[0]:
+                out["guiding_path"] = [s.get("guiding_path", "") for s in samples]
+                keys += [("guiding_label_raw", "guiding_path"), ("guiding_image_raw", "guiding_path")]
+            for key, names in keys:
+                t = stack_raw([s[key] for s in samples], out[names])
                 out[key] = t.pin_memory() if pin else t
             out["crop_pos"] = [tuple(s["crop_pos"]) for s in samples]
             return out
@@ -287,37 +450,114 @@ class DeviceLoader:
     def _stage(self, ids):
         samples = list(self.pool.map(self.ds.__getitem__, ids)) if self.pool else [self.ds[i] for i in ids]
         host = self.collate(samples)
+        dev, ev = self._upload(host)
+        return dev, ev, host       # `host` is kept alive until the copies that read it have run
+
+    def _upload(self, host):
         with torch.cuda.stream(self.side):
             dev = device_preprocess(self.opt, host)
             ev = torch.cuda.Event()
             ev.record(self.side)
-        return dev, ev, host       # `host` is kept alive until the copies that read it have run
+        return dev, ev
+
+    def _hand_over(self, dev, ev):
+        torch.cuda.current_stream().wait_event(ev)
+        for v in dev.values():                       # tensors made on the side stream, used on the compute stream
+            t = v.t if isinstance(v, ops.Labels) else v
+            if isinstance(t, torch.Tensor):
+                t.record_stream(torch.cuda.current_stream())
+        return dev
 
     def __iter__(self):
-        if not self.workers:
-            yield from self._batches()
-            return
-        with ThreadPoolExecutor(self.workers) as self.pool:     # lives as long as the epoch's iterator
-            try:
-                yield from self._batches()
-            finally:
-                self.pool = None
+        return _Epoch(self)
 
-    def _batches(self):
-        idx = self.indices()
-        if hasattr(self.ds, "set_epoch"):
-            self.ds.set_epoch(self.epoch)
-        self.epoch += 1
-        batches = [idx[i:i + self.bs] for i in range(0, len(idx), self.bs)]
-        if self.drop_last:
-            batches = [b for b in batches if len(b) == self.bs]
-        nxt = self._stage(batches[0]) if batches else None
-        for k in range(len(batches)):
-            dev, ev, host = nxt
-            nxt = self._stage(batches[k + 1]) if k + 1 < len(batches) else None
-            torch.cuda.current_stream().wait_event(ev)
-            for v in dev.values():                       # tensors made on the side stream, used on the compute stream
-                t = v.t if isinstance(v, ops.Labels) else v
-                if isinstance(t, torch.Tensor):
-                    t.record_stream(torch.cuda.current_stream())
-            yield dev
+
+class _Epoch:
+    """The iterator of one epoch of a DeviceLoader (an object, not a generator: an exception ends a generator for good).  Batch
+    k + 1 is staged before batch k is handed out.  A batch whose staging raised SkipSampleException is raised from the next()
+    that would have yielded it, and the next() after that yields the following batch, so a consumer that skips (InferenceManager.
+    run) goes on with the epoch.  Any other exception propagates at once and ends the iteration.  Nothing runs before the first
+    next(); the decoding threads live from there until the iteration ends, is closed or is collected."""
+
+    def __init__(self, loader):
+        self.ld, self.batches, self.k, self.nxt, self.pool, self.held = loader, None, 0, None, None, None
+
+    def __iter__(self):
+        return self
+
+    def _start(self):
+        ld = self.ld
+        if ld.workers:
+            ld.pool = self.pool = ThreadPoolExecutor(ld.workers)
+        idx = ld.indices()
+        if hasattr(ld.ds, "set_epoch"):
+            ld.ds.set_epoch(ld.epoch)
+        ld.epoch += 1
+        batches = [idx[i:i + ld.bs] for i in range(0, len(idx), ld.bs)]
+        if ld.drop_last:
+            batches = [b for b in batches if len(b) == ld.bs]
+        self.batches = batches
+        self.nxt = self._stage(0)
+
+    def _stage(self, k):
+        if k >= len(self.batches):
+            return None
+        try:
+            return self.ld._stage(self.batches[k])
+        except SkipSampleException as e:
+            return e
+
+    def close(self):
+        self.batches, self.nxt, self.k, self.held = [], None, 0, None
+        if self.pool is not None:
+            pool, self.pool = self.pool, None
+            if self.ld.pool is pool:
+                self.ld.pool = None
+            pool.shutdown(wait=True)
+
+    __del__ = close
+
+    def __next__(self):
+        try:
+            if self.batches is None:
+                self._start()
+            cur = self.nxt
+            if cur is not None:
+                self.k += 1
+                self.nxt = self._stage(self.k)
+        except BaseException:
+            self.close()
+            raise
+        if cur is None:
+            self.close()
+            raise StopIteration
+        if isinstance(cur, SkipSampleException):
+            raise cur
+        self.held = cur                 # (the pinned host batch lives until the next batch is handed out, as it always did)
+        dev, ev, host = cur
+        return self.ld._hand_over(dev, ev)
+
+
+def create_dataloader(opt, seed=0, shard=(0, 1), raw=True):
+    """data/__init__.py:41-54 over the device loader: the data set of opt.dataset_mode ('celebamaskhq' | 'celeba') on
+    opt.label_dir / opt.image_dir, in the reference's natural order and cut to opt.max_dataset_size, guided if and only if
+    opt.guiding_style_image (opt.identities_file), batched like the reference's DataLoader: batch_size = batchSize, shuffle =
+    not serial_batches, drop_last = isTrain, nThreads decoding threads (at most MAX_WORKERS).  raw=False: FolderDataset (PIL
+    geometry on the host, no threads) instead of RawFolderDataset.  'celeba' resamples its label maps with 'resize'
+    (celeba_dataset.py:53-55): opt.label_preprocess_mode is set to it unless the caller chose one."""
+    mode = getattr(opt, "dataset_mode", "celebamaskhq")
+    if mode not in DATASET_MODES:
+        raise ValueError("dataset_mode must be one of %s, got %r" % (", ".join(DATASET_MODES), mode))
+    label_dir, image_dir = getattr(opt, "label_dir", None), getattr(opt, "image_dir", None)
+    if not label_dir or not image_dir:
+        raise ValueError("create_dataloader needs opt.label_dir and opt.image_dir, got %r and %r" % (label_dir, image_dir))
+    if mode == "celeba" and getattr(opt, "label_preprocess_mode", None) is None:
+        opt.label_preprocess_mode = "resize"
+    size = getattr(opt, "max_dataset_size", None)
+    cls = RawFolderDataset if raw else FolderDataset
+    ds = cls(opt, label_dir, image_dir, seed=seed, dataset_mode=mode, order="natural",
+             max_dataset_size=None if size is None else int(size))
+    print("dataset [%s, %s] of size %d was created" % (cls.__name__, mode, len(ds)))
+    workers = min(int(getattr(opt, "nThreads", 0)), MAX_WORKERS) if raw else 0
+    return DeviceLoader(ds, opt, batch_size=opt.batchSize, shuffle=not getattr(opt, "serial_batches", False), seed=seed,
+                        shard=shard, drop_last=bool(opt.isTrain), workers=workers)

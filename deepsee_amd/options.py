@@ -1,6 +1,7 @@
 """Flat option namespace of the path (the reference threads an argparse.Namespace `opt` through every
 constructor; field list: options/base_options.py, options/train_options.py) and the
 name-keyed presets of options/configurations.py:3-43."""
+import sys
 from types import SimpleNamespace
 
 DEFAULTS = dict(
@@ -20,12 +21,17 @@ DEFAULTS = dict(
     gan_mode="hinge", gradient_clip=-1.0, num_upsampling_layers="normal",
     niter=50, niter_decay=25, gpu_info=False, checkpoints_dir="./checkpoints",
     seed=0,
+    # the data set (options/base_options.py:42,89-98,107 + data/base_dataset.py:28-31; deepsee_amd.data.create_dataloader)
+    phase="train", dataset_mode="celebamaskhq", label_dir=None, image_dir=None, identities_file="",
+    max_dataset_size=sys.maxsize, serial_batches=False, nThreads=0,
     # build-only options (no counterpart in the reference's parser)
     vgg_weights=None,        # path of torchvision's vgg19 state dict (the reference downloads it, architecture.py:154)
     sync_bn=False,           # data-parallel: BatchNorm statistics over the global batch; default sync-free
     sync_bn_clamp=True,      # ... with the reference DP branch's clamp(var, eps) (batchnorm.py:145) instead of var + eps
     preprocess_mode="resize_and_crop", no_flip=False,
     center_crop_size=None,   # options/base_options.py:64 (178 for CelebA): the center_crop* modes of data.RawFolderDataset
+    label_preprocess_mode=None,  # geometry of the label maps in data.device_preprocess; None: as preprocess_mode.  'resize' for
+                                 # dataset_mode='celeba' (celeba_dataset.py:53-55), set by data.create_dataloader
     hip_graphs=True,         # capture the G and the D step as hipGraphs (one per encoder-branch variant and batch shape) and
                              # replay them: 0.5 ms instead of ~60 ms of Python launch enqueue per step
     max_graph_shapes=4,      # ... for at most this many distinct batch shapes (least recently used evicted)

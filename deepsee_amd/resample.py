@@ -123,11 +123,14 @@ def crop_params(opt, size, rng):
     return {"crop_pos": (x, y), "flip": flip}
 
 
-def load_geometry(opt, src_wh, crop_pos=(0, 0)):
-    """get_transform of base_dataset.py:171-201 (with its substring tests on the mode name) for a file of src_wh = (w, h)."""
-    mode = opt.preprocess_mode
-    if mode not in MODES:
-        raise ValueError("preprocess_mode must be one of %s, got %r" % (", ".join(MODES), mode))
+def load_geometry(opt, src_wh, crop_pos=(0, 0), mode=None):
+    """get_transform of base_dataset.py:171-201 (with its substring tests on the mode name) for a file of src_wh = (w, h).
+    mode: get_transform's own preprocess_mode argument (default opt.preprocess_mode); besides MODES it may be 'resize', which
+    celeba_dataset.py:53-55 gives the label maps: resize to load_size and nothing else."""
+    valid = MODES if mode is None else MODES + ("resize",)
+    mode = opt.preprocess_mode if mode is None else mode
+    if mode not in valid:
+        raise ValueError("preprocess_mode must be one of %s, got %r" % (", ".join(valid), mode))
     w, h = int(src_wh[0]), int(src_wh[1])
     box = (0, 0, w, h)
     if "center_crop" in mode:
