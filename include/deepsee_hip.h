@@ -926,13 +926,16 @@ int dsee_spade_resblock_fwd(const dsee_norm_layer* norm_0, const float* w_conv_0
  *       (2048-float slot: dsee_absmax, or the amax_dx of the block behind), -> dx and max |dx| (amax_dx, 2048 floats), and every
  *       parameter gradient whose pointer in `grads` is not NULL: the convolutions' EFFECTIVE weights (apply
  *       dsee_spectral_norm_bwd for weight_orig) and biases, the two NoiseInjection weights, per norm mlp_shared (dw_shared,
- *       db_shared: give both or neither for SPADE), the packed gamma|beta weights dw2a [2C][128][3][3], the style table dtable
+ *       db_shared: each on its own, SPADE and SEAN), the packed gamma|beta weights dw2a [2C][128][3][3], the style table dtable
  *       [N][9][2C][32] (SEAN), and dgamma_beta_sums [2][C] = the per-channel sums of the gamma / beta gradients (the bias
  *       gradient in channel order; dsee_sean_pack_bwd maps it to the packed rows).
  * Both sequence the launches deepsee_amd/ops.py makes on the pre-split fp32 path (same kernels, same operands, same order): the
  * results are bit-identical to the Python module's (tests/test_gpu_ops.py::test_coarse_resblock_training_pair).  Shapes the pre-split
  * kernels do not tile are refused (DSEE_EUNSUPPORTED): C a power of two >= 256, N (H/4) (W/4) % 256 == 0, (H/4) (W/4) % 64 == 0,
- * (36 T / 256) (C / 256) >= 512.  Nothing is allocated, the stream is never synchronised. */
+ * (36 T / 256) (C / 256) >= 512.  The three block entry points check their arguments alike and in this order, before the first
+ * launch and without reading a device pointer: both norms SPADE or both SEAN (DSEE_EINVAL), the shape rule and label_nc in 1..32
+ * (DSEE_EUNSUPPORTED), the label map covers the feature map, the sizes of the workspace and the saved area (DSEE_EINVAL).
+ * Nothing is allocated, the stream is never synchronised. */
 typedef struct dsee_block_noise {
   const float* w_middle;  /* [C] noise_middle.weight (architecture.py:111-112) or NULL */
   uint64_t seed_middle, offset_middle;

@@ -1254,6 +1254,27 @@ def coarse_resblock_training_pair(kind, Lc=19):
     print("coarse training pair (%s): %d tensors compared, not bit-identical: %s" % (kind, len(checks), bad))
     assert not bad, bad
     assert float(amax_dx.max()) == float(x.grad.abs().max())
+    if kind == "spade":
+        # without a table mlp_shared's two gradients are written independently: with one of them not asked for (NULL in both
+        # norms) the other and every other output are what the call with both gave, and the one left out is not written
+        outs = dict(dx=dx, amax_dx=amax_dx, **cg)
+        outs.update({"norm_%d.%s" % (i, k): v for i, z in enumerate((g0, g1)) for k, v in z.items() if v is not None})
+        both = {k: v.clone() for k, v in outs.items()}
+        assert len(both) == 16 and not any(bool(v.isnan().any()) for v in both.values())
+        for drop, key in (("db_shared", "db_sh"), ("dw_shared", "dw_sh")):
+            for v in outs.values():
+                v.fill_(float("nan"))
+            ngs = [NormGrads(*[None if f == drop else getattr(ng, f) for f, _ in NormGrads._fields_]) for ng in (ng0, ng1)]
+            bg1 = BlockGrads(ngs[0], ngs[1], cg["dw0"].data_ptr(), cg["db0"].data_ptr(), cg["dw1"].data_ptr(), cg["db1"].data_ptr(),
+                             cg["dwm"].data_ptr(), cg["dws"].data_ptr())
+            L.call("spade_resblock_bwd", C.byref(n0), w0d, C.byref(n1), w1d, C.byref(bn), labels.t, labels.h, labels.w, shift, Lc, xd,
+                   gout, gout.dsee_amax, C.byref(bg1), dx, amax_dx, 0.2, N, R, R, Cc, saved, C.c_size_t(sbytes), ws,
+                   C.c_size_t(ws.numel()))
+            torch.cuda.synchronize()
+            left_out = ["norm_0." + key, "norm_1." + key]
+            assert all(bool(outs[k].isnan().all()) for k in left_out), drop
+            differ = [k for k, v in outs.items() if k not in left_out and not torch.equal(v, both[k])]
+            assert not differ, (drop, differ)
     blk.zero_grad()
     # shapes the pre-split kernels do not tile are refused, not mis-computed
     with pytest.raises(L.DseeError, match="pre-split training path"):

@@ -79,7 +79,7 @@ def test_dontcare_label_with_a_label_nc_sized_encoder_input_is_refused_at_build(
 
 
 def test_coarse_entry_points_reject_more_than_32_classes_with_and_without_table():
-    """dsee_sean_norm_fwd and the two training entry points of the residual block (train_shape_ok) return DSEE_EUNSUPPORTED for
+    """dsee_sean_norm_fwd and the two training entry points of the residual block (block_args_ok) return DSEE_EUNSUPPORTED for
     label_nc = 33 whether or not there is a style table, at shapes they otherwise accept, before they touch a pointer."""
     from deepsee_amd import lib as L
     so = L.lib()

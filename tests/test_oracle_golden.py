@@ -14,7 +14,7 @@ from oracle import deepsee_oracle as O
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 CASES = sorted(os.path.basename(p)[:-5] for p in glob.glob(os.path.join(GOLD, "*.json"))
-               if not p.endswith(("layer_kats.json", "host_logic.json", "metrics.json")))
+               if not p.endswith(("layer_kats.json", "host_logic.json", "metrics.json", "coarse_workspace.json")))
 
 # Bounds: losses / outputs are tight; gradients are bounded by the reference's OWN noise floor
 # (oracle/noise_floor.py: a 1e-7 relative input perturbation moves G-step grads by 2.6e-3 and
