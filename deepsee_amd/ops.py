@@ -9,6 +9,7 @@ import os
 import ctypes as C
 
 import threading
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -644,6 +645,25 @@ def _gemm_name(split):
 
 FUSED_V_BOUND = 100.0       # |B^T d B| <= 100 max|d| for F(4x4,3x3): scale of a pre-split V from max |input|
 
+# the four storage forms of a Winograd-domain operand (V of an input, dM = A dY A^T of an output gradient)
+FP32 = "fp32"               # [36][t][c] fp32; amax = its device maximum (None where no fp16 kernel will scale by it)
+F16X2 = "f16x2"             # two scaled fp16 terms per element, written by the transform; amax = max |input| it was scaled with
+F16P = "f16p"               # ONE scaled fp16 term per element (16-bit storage mode); amax as for F16X2
+BF16X3_T = "bf16x3_t"       # transposed, three bf16 terms per element (weight-gradient mode 1); no maximum
+WinoOperand = NamedTuple("WinoOperand", [("data", torch.Tensor), ("amax", Optional[torch.Tensor]), ("form", str)])
+
+
+def save_with_operand(ctx, op, *tensors):
+    """ctx.save_for_backward(*tensors) plus one WinoOperand (or None): its tensors are saved with the others, its form on ctx."""
+    ctx.operand_form = None if op is None else op.form
+    ctx.save_for_backward(*tensors, *((None, None) if op is None else op[:2]))
+
+
+def saved_with_operand(ctx):
+    """(tensors, operand) as save_with_operand() stored them"""
+    *tensors, data, amax = ctx.saved_tensors
+    return tensors, (None if data is None else WinoOperand(data, amax, ctx.operand_form))
+
 
 def _presplit_ok(xc, t, t_g, r_s, k_s=0, keep=False):
     """dsee_gemm_f16x2_pre takes 256 x 256 tiles only; below 512 of them the 128 x 128 kernel fills the chip better.
@@ -672,74 +692,60 @@ def _pk_ok(xc, t_g, r_s, k_s):
 def _wino_vgemm(xc, nb, h, wd, k_s, u, r_s, rows, kp, per_image, split, keep=None, u_amax=None):
     """(M [36][t][r_s], mscale) = V(xc) x U: input transform of `nb` images + the 36 (x nb with per-image weights) GEMMs.
     mscale: None (M is fp32) or the device scalar that rescales the fp16 M of the half-precision mode.
-    `keep` (a list) receives (V, amax_V) when V exists in fp32 (it is the weight gradient's Q operand)."""
+    `keep` (a list) receives V as a WinoOperand where the weight gradient can read it as its Q operand."""
     tpi = (h // 4) * (wd // 4)
     t = nb * tpi
     groups, t_g = (36 * nb, tpi) if per_image else (36, t)
     m = torch.empty(36, t, r_s, dtype=torch.float16, device="cuda") if split in (3, 4) else new(36, t, r_s)
-    ms = None
-    if split == 4:
-        # 16-bit storage: V leaves the transform as ONE scaled fp16 term per element (2 bytes), the GEMM streams it and the
-        # packed one-term weights without conversion and writes the product as scaled fp16
-        ax = xc.dsee_amax
-        v1, ms = _i16(36 * t * k_s), amax_slot()
-        L.call("wino43_input_f16p", xc, v1, nb, h, wd, k_s, ax, FUSED_V_BOUND)
-        with _timed("winograd_gemm_f16_1term_packed", 2.0 * 36 * t * k_s * r_s,
-                    2.0 * 36 * t * k_s + 2.0 * groups * rows * k_s + 2.0 * 36 * t * r_s):
-            L.call(_gemm_pre("gemm_f16p_pre", k_s, r_s), v1, u, m, 36 * t, r_s, k_s, t_g, rows, ax, FUSED_V_BOUND, u_amax, ms)
-        if keep is not None:
-            keep.append((v1, ax, "pk"))     # (packed one-term V, max |x|, marker): the weight gradient's Q operand as it is
-    elif split == 3:
-        v, va, ms = new(36, t, k_s), amax_slot(), amax_slot()
-        L.call("wino43_input", xc, v, nb, h, wd, k_s, va)
-        with _timed(_gemm_name(3), 2.0 * 36 * t * k_s * r_s, _gemm_bytes(t, k_s, r_s, groups, rows, 3)):
-            L.call("gemm_f16_af32", v, u, m, 36 * t, r_s, k_s, t_g, rows, 0, va, u_amax, 1, ms)
-        if keep is not None:
-            keep.append((v, va))
-    elif split == 2 and _presplit_ok(xc, t, t_g, r_s, k_s, keep is not None):
-        # the input's maximum is known (written by the kernel that produced it): the transform writes V already split, with
-        # the scale fixed by the bound |B^T d B| <= 100 max|d|, and the GEMM streams it without staging or conversion
-        ax = xc.dsee_amax
-        v2 = _i16(36 * t * k_s * 2)
-        L.call("wino43_input_f16x2", xc, v2, nb, h, wd, k_s, ax, FUSED_V_BOUND)
-        with _timed(_gemm_name(2), 2.0 * 36 * t * k_s * r_s, _gemm_bytes(t, k_s, r_s, groups, rows, 2)):
-            L.call(_gemm_pre("gemm_f16x2_pre", k_s, r_s), v2, u, m, 36 * t, r_s, k_s, t_g, rows, ax, FUSED_V_BOUND, u_amax)
-        if keep is not None:
-            keep.append((v2, ax, True))      # (pre-split V, max |x|, marker): the weight gradient's Q operand as it is
-    elif split == 2:
-        v, va = new(36, t, k_s), amax_slot()
-        L.call("wino43_input", xc, v, nb, h, wd, k_s, va)
-        with _timed(_gemm_name(2), 2.0 * 36 * t * k_s * r_s, _gemm_bytes(t, k_s, r_s, groups, rows, 2)):
-            L.call("gemm_f16x2_af32", v, u, m, 36 * t, r_s, k_s, t_g, rows, 0, va, u_amax)
-        if keep is not None:
-            keep.append((v, va))
-    elif split and P().gemm_af32 and k_s * 4 * 256 < 0x7FFFFFFF:
-        v = new(36, t, k_s)
-        L.call("wino43_input", xc, v, nb, h, wd, k_s, None)
-        with _timed(_gemm_name(1), 2.0 * 36 * t * k_s * r_s, _gemm_bytes(t, k_s, r_s, groups, rows, 1)):
-            L.call("gemm_bf16x3_af32", v, u, m, 36 * t, r_s, k_s, t_g, rows, 0)
-        if keep is not None:
-            keep.append((v, None))
-    elif split:
+    ms = amax_slot() if split in (3, 4) else None
+    shape, flops = (36 * t, r_s, k_s, t_g, rows), 2.0 * 36 * t * k_s * r_s
+    if split == 1 and not (P().gemm_af32 and k_s * 4 * 256 < 0x7FFFFFFF):
         v = _i16(36 * t * k_s * 3)
         L.call("wino43_input_split", xc, v, nb, h, wd, k_s)
         # algorithmic HBM bytes: A3 (6 B/element) + B3 + C (fp32)
-        with _timed(_gemm_name(1), 2.0 * 36 * t * k_s * r_s,
-                    6.0 * 36 * t * k_s + 6.0 * groups * rows * k_s + 4.0 * 36 * t * r_s):
-            L.call("gemm_bf16x3", v, u, m, 36 * t, r_s, k_s, t_g, rows, 0)
+        with _timed(_gemm_name(1), flops, 6.0 * 36 * t * k_s + 6.0 * groups * rows * k_s + 4.0 * 36 * t * r_s):
+            L.call("gemm_bf16x3", v, u, m, *shape, 0)
+        return m, ms
+    if split == 4 or (split == 2 and _presplit_ok(xc, t, t_g, r_s, k_s, keep is not None)):
+        # the input's maximum is known (written by its producer): the transform writes V already split (two scaled fp16 terms per
+        # element; ONE in the 16-bit storage mode) with the scale fixed by |B^T d B| <= 100 max|d|; the GEMM streams it as it is
+        pk = split == 4
+        v = WinoOperand(_i16(36 * t * k_s * (1 if pk else 2)), xc.dsee_amax, F16P if pk else F16X2)
+        L.call("wino43_input_f16p" if pk else "wino43_input_f16x2", xc, v.data, nb, h, wd, k_s, v.amax, FUSED_V_BOUND)
     else:
-        v = new(36, t, k_s)
-        L.call("wino43_input", xc, v, nb, h, wd, k_s, None)
+        v = WinoOperand(new(36, t, k_s), amax_slot() if split in (2, 3) else None, FP32)     # (its maximum: the fp16 GEMMs' scale)
+        L.call("wino43_input", xc, v.data, nb, h, wd, k_s, v.amax)
+    if not split:
         g = L.ConvGeom(groups, t_g, 1, k_s, t_g, 1, r_s, 1, 1, 1, 0, 1, 0, 0, 1)
-        with _timed("winograd_gemm_128x128(igemm,36 groups)", 2.0 * 36 * t * k_s * r_s):
-            L.call("conv2d_fwd_grouped", C.byref(g), v, u, rows * kp, m)
+        with _timed("winograd_gemm_128x128(igemm,36 groups)", flops):
+            L.call("conv2d_fwd_grouped", C.byref(g), v.data, u, rows * kp, m)
+        return m, ms
+    with _timed(_gemm_name(split), flops, _gemm_bytes(t, k_s, r_s, groups, rows, split)):
+        _wino_gemm(v, FUSED_V_BOUND, u, u_amax, m, shape, split, ms)
+    if keep is not None:
+        keep.append(v)         # the weight gradient's Q operand as it is
     return m, ms
+
+
+def _wino_gemm(a, bound, u, u_amax, m, shape, split, ms):
+    """m = a x u, `shape` = (M, N, K, rows per group, weight rows) of the grouped NT GEMM: the kernel by the form of operand
+    a (pre-split: scaled by `bound` x a.amax) and, for an fp32 a, by the `split` kind of u; `ms`: slot for an fp16 m's scale."""
+    if a.form == F16P:
+        L.call(_gemm_pre("gemm_f16p_pre", shape[2], shape[1]), a.data, u, m, *shape, a.amax, bound, u_amax, ms)
+    elif a.form == F16X2:
+        L.call(_gemm_pre("gemm_f16x2_pre", shape[2], shape[1]), a.data, u, m, *shape, a.amax, bound, u_amax)
+    elif split == 3:
+        L.call("gemm_f16_af32", a.data, u, m, *shape, 0, a.amax, u_amax, 1, ms)
+    elif split == 2:
+        L.call("gemm_f16x2_af32", a.data, u, m, *shape, 0, a.amax, u_amax)
+    else:
+        L.call("gemm_bf16x3_af32", a.data, u, m, *shape, 0)
 
 
 def _wino_conv(x, w, n, h, wd, cin_s, cout_s, transpose_flip, bias=None, res=None, act=L.ACT_NONE, res_ld=0, keep=None,
                noise=None, res_noise=None, stats=False):
     """y = conv3x3(x, w) (transpose_flip: data gradient of that conv) through 36 Winograd-domain GEMMs.
-    `keep`: list that receives (V, amax_V) of the input when the whole batch went through in one pass.
+    `keep`: list that receives the WinoOperand V of the input when the whole batch went through in one pass.
     `noise` = (noise_w [r_s], PhiloxNormal of y's shape): y += noise_w * eps in the output transform;
     `res_noise`: the same on the residual (res + w * eps is what gets added)."""
     co, ci = w.shape[0], w.shape[1]
@@ -809,81 +815,69 @@ def _dout_sums_ok(n, nb, cout_s, mode):
 DM_BOUND = 1.0
 
 
-def _is_pk(v):
-    """(tensor, amax, "pk"): a packed one-term operand of the 16-bit storage mode"""
-    return v is not None and len(v) == 3 and v[2] == "pk"
+# `split` argument of dsee_wino43_wgrad[_table] per (V form, dM form); None: the weight-gradient mode decides (_wgrad_split)
+_WGRAD_CODES = {(FP32, FP32): None, (BF16X3_T, BF16X3_T): None, (F16X2, FP32): 5, (F16X2, F16X2): 6, (F16P, F16P): 7}
 
 
 def _wgrad_code(v, dm, mode):
-    """`split` argument of dsee_wino43_wgrad[_table] for the operand forms at hand"""
-    if _is_pk(v):
-        assert _is_pk(dm)
-        return 7
-    if len(v) == 3:
-        return 6 if len(dm) == 3 else 5
-    return _wgrad_split(mode)
+    """`split` argument of dsee_wino43_wgrad[_table] for the operand forms at hand; a pairing no kernel takes raises
+    (a packed one-term V needs a packed one-term dM: dsee_gemm_f16p_tn_pqpre)."""
+    if (v.form, dm.form) not in _WGRAD_CODES or (v.form == BF16X3_T) != (mode == 1):
+        raise ValueError("no weight-gradient kernel for V %s x dM %s in mode %d" % (v.form, dm.form, mode))
+    return _WGRAD_CODES[(v.form, dm.form)] or _wgrad_split(mode)
+
+
+def _fp16_amax_needed():
+    """fp32 operands get their maximum measured: an fp16 GEMM will scale them by it"""
+    return P().gemm_split and (P().gemm_f16x2 or P().half)
+
+
+def _wino_dout(gc, nb, h, wd, cout_s, form, sums=None):
+    """dM = A dY A^T of one image chunk as a WinoOperand of `form`: FP32, or F16X2 / F16P scaled by the maximum dY carries.
+    `sums`: {"bias": bool, "n0": PhiloxNormal | None, "n1": ...} -- the bias gradient and the NoiseInjection weight gradients
+    of the layer, computed by the same pass and returned in the same dict as "dbias" / "dn0" / "dn1"."""
+    t = nb * (h // 4) * (wd // 4)
+    n0, n1 = (sums.get("n0"), sums.get("n1")) if sums else (None, None)
+    db = new(cout_s) if sums and sums.get("bias") else None
+    dn0, dn1 = (new(cout_s) if n0 is not None else None), (new(cout_s) if n1 is not None else None)
+    if sums:
+        sums.update(dbias=db, dn0=dn0, dn1=dn1)
+    r0, r1 = ((r.seed, r.offset) if r is not None else (0, 0) for r in (n0, n1))
+    tail = (db, dn0, *r0, dn1, *r1)          # the seven trailing arguments of the three kernels that also sum
+    if form != FP32:
+        dm = WinoOperand(_i16(36 * t * cout_s * (1 if form == F16P else 2)), carried_amax(gc), form)
+        any_sum = db is not None or dn0 is not None or dn1 is not None
+        ws = scratch(L.lib().dsee_wino43_dout_f16x2_workspace(), "doutsums2") if any_sum else None
+        L.call("wino43_dout_f16p" if form == F16P else "wino43_dout_f16x2", gc, dm.data, nb, h, wd, cout_s, dm.amax, DM_BOUND, ws,
+               *tail)
+        return dm
+    dm = WinoOperand(new(36, t, cout_s), amax_slot() if _fp16_amax_needed() else None, FP32)
+    if sums:
+        ws = scratch(L.lib().dsee_wino43_dout_sums_workspace(cout_s), "doutsums")
+        L.call("wino43_dout_sums", gc, dm.data, nb, h, wd, cout_s, dm.amax, ws, *tail)
+    else:
+        L.call("wino43_dout", gc, dm.data, nb, h, wd, cout_s, dm.amax)
+    return dm
 
 
 def _wino_wgrad_operands(xc, gc, nb, h, wd, cin_s, cout_s, mode, v=None, dm=None, sums=None, pre_dm=False):
-    """((V, amax_V), (dM, amax_dM)) of one image chunk for the Winograd-domain weight gradient: fp32 rows (modes 0, 2;
-    `v` may be the (V, amax) the forward pass kept, `dm` the (A dY A^T, amax) its producer already wrote) or transposed
-    bf16x3 (mode 1, no maxima).  `sums`: {"bias": bool, "n0": PhiloxNormal | None, "n1": ...} -- the bias gradient and the
-    NoiseInjection weight gradients of the layer, computed by the pass that transforms dY and returned in the same dict as
-    "dbias" / "dn0" / "dn1"."""
+    """(V, dM) of one image chunk for the Winograd-domain weight gradient, as WinoOperands: transposed bf16x3 in mode 1;
+    else `v` may be the V the forward pass kept and `dm` the A dY A^T its producer already wrote.  `pre_dm`: dM may leave
+    its transform in the form of a pre-split `v` (when dY carries its maximum).  `sums`: see _wino_dout."""
     t = nb * (h // 4) * (wd // 4)
     if mode == 1:
-        v, dm = _i16(36 * t * cin_s * 3), _i16(36 * t * cout_s * 3)
-        L.call("wino43_input_split_t", xc, v, nb, h, wd, cin_s)
-        L.call("wino43_dout_split_t", gc, dm, nb, h, wd, cout_s)
-        return (v, None), (dm, None)
-    need = P().gemm_split and (P().gemm_f16x2 or P().half)   # maxima for the fp16 operand scales
-    ga = carried_amax(gc) if gc is not None else None
-    if _is_pk(v) and not _is_pk(dm) and not (dm is None and pre_dm and ga is not None):
+        vt, dmt = _i16(36 * t * cin_s * 3), _i16(36 * t * cout_s * 3)
+        L.call("wino43_input_split_t", xc, vt, nb, h, wd, cin_s)
+        L.call("wino43_dout_split_t", gc, dmt, nb, h, wd, cout_s)
+        return WinoOperand(vt, None, BF16X3_T), WinoOperand(dmt, None, BF16X3_T)
+    pre_dm = dm is None and pre_dm and carried_amax(gc) is not None
+    if v is not None and v.form == F16P and not pre_dm and not (dm is not None and dm.form == F16P):
         v = None       # a packed one-term V needs a packed one-term dM (dsee_gemm_f16p_tn_pqpre): transform x again in fp32
-    if v is not None and len(v) == 3:
-        pass                                     # the forward's pre-split V2 (dsee_wino43_wgrad split = 5)
-    elif v is None or (need and v[1] is None):
-        v = (new(36, t, cin_s), amax_slot() if need else None)
-        L.call("wino43_input", xc, v[0], nb, h, wd, cin_s, v[1])
-    if dm is None and pre_dm and ga is not None and _is_pk(v):
-        # 16-bit storage: A dY A^T as ONE scaled fp16 term per element, for the same two consumers
-        dm1 = _i16(36 * t * cout_s)
-        n0, n1 = (sums.get("n0"), sums.get("n1")) if sums else (None, None)
-        if sums:
-            sums["dbias"] = new(cout_s) if sums.get("bias") else None
-            sums["dn0"], sums["dn1"] = (new(cout_s) if n0 is not None else None), (new(cout_s) if n1 is not None else None)
-        any_sum = bool(sums) and (sums["dbias"] is not None or n0 is not None or n1 is not None)
-        ws = scratch(L.lib().dsee_wino43_dout_f16x2_workspace(), "doutsums2") if any_sum else None
-        L.call("wino43_dout_f16p", gc, dm1, nb, h, wd, cout_s, ga, DM_BOUND, ws, sums["dbias"] if sums else None,
-               sums["dn0"] if sums else None, n0.seed if n0 is not None else 0, n0.offset if n0 is not None else 0,
-               sums["dn1"] if sums else None, n1.seed if n1 is not None else 0, n1.offset if n1 is not None else 0)
-        dm = (dm1, ga, "pk")
-    elif dm is None and pre_dm and ga is not None and v is not None and len(v) == 3:
-        # dY's maximum is known (its producer wrote it): A dY A^T leaves the transform pre-split, for the weight gradient's
-        # P operand and the adjoint data-gradient GEMM's A operand alike
-        dm2 = _i16(36 * t * cout_s * 2)
-        n0, n1 = (sums.get("n0"), sums.get("n1")) if sums else (None, None)
-        if sums:
-            sums["dbias"] = new(cout_s) if sums.get("bias") else None
-            sums["dn0"], sums["dn1"] = (new(cout_s) if n0 is not None else None), (new(cout_s) if n1 is not None else None)
-        any_sum = bool(sums) and (sums["dbias"] is not None or n0 is not None or n1 is not None)
-        ws = scratch(L.lib().dsee_wino43_dout_f16x2_workspace(), "doutsums2") if any_sum else None
-        L.call("wino43_dout_f16x2", gc, dm2, nb, h, wd, cout_s, ga, DM_BOUND, ws, sums["dbias"] if sums else None,
-               sums["dn0"] if sums else None, n0.seed if n0 is not None else 0, n0.offset if n0 is not None else 0,
-               sums["dn1"] if sums else None, n1.seed if n1 is not None else 0, n1.offset if n1 is not None else 0)
-        dm = (dm2, ga, True)
-    elif dm is None:
-        dm = (new(36, t, cout_s), amax_slot() if need else None)
-        if sums:
-            n0, n1 = sums.get("n0"), sums.get("n1")
-            sums["dbias"] = new(cout_s) if sums.get("bias") else None
-            sums["dn0"], sums["dn1"] = (new(cout_s) if n0 is not None else None), (new(cout_s) if n1 is not None else None)
-            ws = scratch(L.lib().dsee_wino43_dout_sums_workspace(cout_s), "doutsums")
-            L.call("wino43_dout_sums", gc, dm[0], nb, h, wd, cout_s, dm[1], ws, sums["dbias"],
-                   sums["dn0"], n0.seed if n0 is not None else 0, n0.offset if n0 is not None else 0,
-                   sums["dn1"], n1.seed if n1 is not None else 0, n1.offset if n1 is not None else 0)
-        else:
-            L.call("wino43_dout", gc, dm[0], nb, h, wd, cout_s, dm[1])
+    if v is None or (v.form == FP32 and v.amax is None and _fp16_amax_needed()):
+        v = WinoOperand(new(36, t, cin_s), amax_slot() if _fp16_amax_needed() else None, FP32)
+        L.call("wino43_input", xc, v.data, nb, h, wd, cin_s, v.amax)
+    if dm is None:
+        dm = _wino_dout(gc, nb, h, wd, cout_s, v.form if pre_dm else FP32, sums)
     return v, dm
 
 
@@ -893,53 +887,41 @@ def _adjoint_ok(k_s, r_s):
 
 
 def _wino_dgrad_from_dm(dm, u_t, nb, h, wd, k_s, r_s, rows, mask=None, mask_ld=0):
-    """dx [nb,h,wd,r_s] of a 3x3 convolution from dm = (dM [36][t][k_s] = A dY A^T, amax): one grouped GEMM with the
+    """dx [nb,h,wd,r_s] of a 3x3 convolution from the WinoOperand dm (dM [36][t][k_s] = A dY A^T): one grouped GEMM with the
     transposed forward weights u_t = (U^T [36][rows][k_s] split, amax) and the overlap-add of the patches B dV B^T."""
     t = nb * (h // 4) * (wd // 4)
-    split = 4 if _is_pk(dm) else _split_kind(k_s, r_s)          # (the kind u_t was built with)
+    split = 4 if dm.form == F16P else _split_kind(k_s, r_s)          # (the kind u_t was built with)
     dv = torch.empty(36, t, r_s, dtype=torch.float16, device="cuda") if split in (3, 4) else new(36, t, r_s)
     dvs = amax_slot() if split in (3, 4) else None
     with _timed(_gemm_name(split), 2.0 * 36 * t * k_s * r_s, _gemm_bytes(t, k_s, r_s, 36, rows, split)):
-        if split == 4:
-            L.call(_gemm_pre("gemm_f16p_pre", k_s, r_s), dm[0], u_t[0], dv, 36 * t, r_s, k_s, t, rows, dm[1], DM_BOUND, u_t[1], dvs)
-        elif len(dm) == 3:
-            L.call(_gemm_pre("gemm_f16x2_pre", k_s, r_s), dm[0], u_t[0], dv, 36 * t, r_s, k_s, t, rows, dm[1], DM_BOUND, u_t[1])
-        elif split == 3:
-            L.call("gemm_f16_af32", dm[0], u_t[0], dv, 36 * t, r_s, k_s, t, rows, 0, dm[1], u_t[1], 1, dvs)
-        elif split == 2:
-            L.call("gemm_f16x2_af32", dm[0], u_t[0], dv, 36 * t, r_s, k_s, t, rows, 0, dm[1], u_t[1])
-        else:
-            L.call("gemm_bf16x3_af32", dm[0], u_t[0], dv, 36 * t, r_s, k_s, t, rows, 0)
+        _wino_gemm(dm, DM_BOUND, *u_t, dv, (36 * t, r_s, k_s, t, rows), split, dvs)
     dx = new(nb, h, wd, r_s)
+    # max |dx| rides along: dx is the gradient w.r.t. a norm's output (bound of that norm's gamma/beta gradient) or, in the masked
+    # form, the embedding's gradient (the dout operand of mlp_shared's weight gradient)
+    tag_amax(dx, amax_slot())
     if mask is None and dvs is None and P().presplit_dm:
-        tag_amax(dx, amax_slot())      # (dx is the gradient w.r.t. a norm's output: bound of that norm's gamma/beta gradient)
         L.call("wino43_input_adjoint_amax", dv, dx, nb, h, wd, r_s, dx.dsee_amax)
     elif mask is None and split == 4 and P().presplit_dm:
-        tag_amax(dx, amax_slot())
         L.call("wino43_input_adjoint_amax_f16", dv, dx, nb, h, wd, r_s, dvs, dx.dsee_amax)
     else:
-        # (masked form: dx is the embedding's gradient, the dout operand of mlp_shared's weight gradient -- its maximum rides along)
-        tag_amax(dx, amax_slot())
         L.call("wino43_input_adjoint", dv, mask, mask_ld, dx, nb, h, wd, r_s, dvs, dx.dsee_amax)
     return dx
 
 
 def _wino_wgrad(x, g, n, h, wd, cin_s, cout_s, co, ci, v_fwd=None, w_for_dx=None, sums=None):
-    """dw OIHW of conv3x3(x, w) given g = dL/dy, reduced over tiles in the Winograd domain.  `v_fwd`: the (V, amax) of
+    """dw OIHW of conv3x3(x, w) given g = dL/dy, reduced over tiles in the Winograd domain.  `v_fwd`: the WinoOperand V of
     x kept by the forward pass (used when the weight gradient takes fp32 operands and runs in one pass).
     `w_for_dx` (the weight): also return dx, computed from the same dM in the adjoint form -> (dw, dx)."""
     nb = _wino_chunk(n, h, wd, max(cin_s, cout_s))
-    t = nb * (h // 4) * (wd // 4)
-    mode = _wgrad_mode(cin_s, cout_s)
+    t, mode = nb * (h // 4) * (wd // 4), _wgrad_mode(cin_s, cout_s)
     nbytes = L.lib().dsee_wino43_wgrad_workspace(C.c_long(t), cin_s, cout_s)
     ws = scratch(nbytes, "wgrad")
-    total = None
-    with_dx = w_for_dx is not None
+    total, with_dx = None, w_for_dx is not None
     assert not with_dx or (mode != 1 and _adjoint_ok(cout_s, cin_s))
     # 16-bit storage mode: the forward kept a packed one-term V -> A dY A^T packed one-term too (wgrad split 7, adjoint GEMM on
     # dsee_gemm_f16p_pre), when dY's maximum is known
-    pk = (_is_pk(v_fwd) and P().presplit_dm and mode == 2 and nb == n and carried_amax(g) is not None and t % 256 == 0
-          and cout_s % 32 == 0 and (not with_dx or cin_s % 128 == 0))
+    pk = (v_fwd is not None and v_fwd.form == F16P and P().presplit_dm and mode == 2 and nb == n and carried_amax(g) is not None
+          and t % 256 == 0 and cout_s % 32 == 0 and (not with_dx or cin_s % 128 == 0))
     if with_dx:
         rows_t = L.wrows(cin_s)
         u_t = _wino_u(w_for_dx, co, ci, 2, rows_t, L.kpad(1, 1, cout_s), 4 if pk else _split_kind(cout_s, cin_s))
@@ -954,7 +936,8 @@ def _wino_wgrad(x, g, n, h, wd, cin_s, cout_s, co, ci, v_fwd=None, w_for_dx=None
                                      v_fwd if (mode == 2 and nb == n) else None, sums=sums, pre_dm=pre_dm)
         dw = new(co, ci, 3, 3)
         with _timed(_wgrad_name(mode), 2.0 * 36 * t * cin_s * cout_s):
-            L.call("wino43_wgrad", v[0], dm[0], ws, nbytes, dw, t, cin_s, cout_s, co, ci, _wgrad_code(v, dm, mode), v[1], dm[1])
+            L.call("wino43_wgrad", v.data, dm.data, ws, nbytes, dw, t, cin_s, cout_s, co, ci, _wgrad_code(v, dm, mode), v.amax,
+                   dm.amax)
         total = dw if total is None else total.add_(dw)
         if with_dx:
             dxc = _wino_dgrad_from_dm(dm, u_t, nb, h, wd, cout_s, cin_s, rows_t)
@@ -1019,17 +1002,15 @@ class Conv2d(torch.autograd.Function):
         ctx.noise = noise_eps if noise_w is not None else None
         ctx.res_noise = res_noise_eps if res_noise_w is not None else None
         ctx.res_sink = res_sink
-        ctx.v_kind = vkeep[2] if (vkeep and len(vkeep) == 3) else None     # True: fp16x2 pre-split, "pk": packed one-term
-        ctx.save_for_backward(x, w, out if act != L.ACT_NONE else None, *(vkeep[:2] if vkeep else (None, None)))
+        save_with_operand(ctx, vkeep, x, w, out if act != L.ACT_NONE else None)
         return out
 
     @staticmethod
     @_under_plan
     def backward(ctx, dy):
-        x, w, out, vk, vk_amax = ctx.saved_tensors
+        (x, w, out), vkeep = saved_with_operand(ctx)
         w.dsee_amax, w.dsee_u = ctx.w_amax, ctx.w_u
         _bind_rng(ctx.noise, ctx.res_noise)
-        vkeep = ((vk, vk_amax, ctx.v_kind) if ctx.v_kind else (vk, vk_amax)) if vk is not None else None
         geom = ctx.geom
         co, ci, kh, kw = w.shape
         dy = dy.contiguous()
@@ -1869,16 +1850,16 @@ def modulate_bwd(dh, out, x, scale, mean, invstd, rows, cfg, as_dm=False, add=No
         ga = amax_slot()
         L.call("amax_product", dha, xhat_amax, 1.0, ga)
         pk = P().half      # 16-bit storage mode: one scaled fp16 term per element (dsee_modulate_bwd_reduce_wino_f16p)
-        dm = (_i16(36 * t * rows * (1 if pk else 2)), ga, "pk" if pk else True)
+        dm = WinoOperand(_i16(36 * t * rows * (1 if pk else 2)), ga, F16P if pk else F16X2)
         ws = scratch(L.lib().dsee_modulate_bwd_wino_workspace(n, h, w, c), "norm")
         L.call("modulate_bwd_reduce_wino_f16p" if pk else "modulate_bwd_reduce_wino_f16x2", dh.contiguous(),
-               None if mask is not None else out, x, scale, mean, invstd, dm[0], rows, sums, n, h, w, c, LRELU_SLOPE, ws, ga,
+               None if mask is not None else out, x, scale, mean, invstd, dm.data, rows, sums, n, h, w, c, LRELU_SLOPE, ws, ga,
                DM_BOUND, mask)
     elif as_dm:
-        dm = (new(36, t, rows), amax_slot() if (P().gemm_split and (P().gemm_f16x2 or P().half)) else None)
+        dm = WinoOperand(new(36, t, rows), amax_slot() if _fp16_amax_needed() else None, FP32)
         ws = scratch(_wino_ws(n, h, w, c, sg), "norm")
-        _call_sg("modulate_bwd_reduce_wino", sg, (dh.contiguous(), out, x, scale, mean, invstd, dm[0], rows, sums, n, h, w, c),
-                 (LRELU_SLOPE, ws, dm[1]))
+        _call_sg("modulate_bwd_reduce_wino", sg, (dh.contiguous(), out, x, scale, mean, invstd, dm.data, rows, sums, n, h, w, c),
+                 (LRELU_SLOPE, ws, dm.amax))
     else:
         dgb = (torch.zeros if c % 64 else torch.empty)(n, h, w, rows, dtype=torch.float32, device=x.device)
         ws = scratch(L.lib().dsee_norm_workspace(n, h * w, c, sg), "norm")
@@ -1898,6 +1879,22 @@ def modulate_bwd(dh, out, x, scale, mean, invstd, rows, cfg, as_dm=False, add=No
     return dx, dgb, sums[2 * sg:2 * sg + 2], dm
 
 
+def _norm_product_direct(geom, cat, w, table, ca, b2, x, mean, invstd, out, scale, add_one):
+    """out = lrelu(norm(x) * (gamma + add_one) + beta), (gamma | beta) = conv3x3(cat, w (+ per-image `table` over the one-hot
+    channels behind the first `ca`)) + b2 formed in the epilogue of the direct convolution kernel"""
+    wp = _pack_fwd(w, w.shape[1], geom.korder) if w is not None else None
+    with _timed(_variant(geom, True), _flops(geom)):
+        _call_sg("conv2d_modulate_fwd", stat_groups(mean),
+                 (C.byref(geom), cat, wp, table, ca, b2.contiguous(), x, mean, invstd, out, scale, x.shape[3]),
+                 (float(add_one), LRELU_SLOPE))
+
+
+def _packed_bias_grad(cs, c):
+    """gradient of the packed (gamma | beta) bias b2 from the two column sums cs [2][C] of the norm backward"""
+    idx, _ = packed_perm(c, cs.device)
+    return torch.cat([cs.reshape(-1), torch.zeros(1, device=cs.device)]).index_select(0, idx)
+
+
 class SpadeNormAct(torch.autograd.Function):
     """h = lrelu(BN(x) * (conv_gamma(cat) + add_one) + conv_beta(cat)) with gamma/beta formed inside the GEMM
     epilogue; BN = sync-free batch statistics in training, running statistics in eval.  running_mean None: InstanceNorm
@@ -1915,11 +1912,7 @@ class SpadeNormAct(torch.autograd.Function):
         assert geom.Ho == h and geom.Wo == w
         w2 = w2.contiguous()
         out, scale = torch.empty_like(x), torch.empty_like(x)
-        wp = _pack_fwd(w2, kin, geom.korder)
-        with _timed(_variant(geom, True), _flops(geom)):
-            _call_sg("conv2d_modulate_fwd", stat_groups(mean),
-                     (C.byref(geom), cat, wp, None, 0, b2.contiguous(), x, mean, invstd, out, scale, c),
-                     (float(add_one), LRELU_SLOPE))
+        _norm_product_direct(geom, cat, w2, None, 0, b2, x, mean, invstd, out, scale, add_one)
         ctx.geom = geom
         ctx.save_for_backward(x, cat, w2, out, scale, mean, invstd)
         return out
@@ -1945,8 +1938,7 @@ class SpadeNormAct(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             dw2 = wgrad_raw(cat, dgb, geom, rows, kin, 3, 3)
         if ctx.needs_input_grad[3]:
-            idx, _ = packed_perm(c, x.device)
-            db2 = torch.cat([cs.reshape(-1), torch.zeros(1, device=x.device)]).index_select(0, idx)
+            db2 = _packed_bias_grad(cs, c)
         return dx, dcat, dw2, db2, None, None, None, None, None, None
 
 
@@ -1963,6 +1955,197 @@ def _norm_plan(plan):
     return plan.replace(half=False) if (plan.half and not plan.half_norms) else plan
 
 
+def _norm_cat(w_sh, b_sh, labels, shift, n, h, w, has_a, has_t, cat_ups):
+    """(cat, max |cat| or None, actv_low or None): the gamma/beta convolution's input cat [n,h,w,ld] = [ReLU(mlp_shared(one-hot
+    label)) (128, `has_a`) ; one-hot label (32, `has_t`)].  `cat_ups`: the embedding is computed at the capped resolution
+    (actv_low) and nearest-upsampled."""
+    nc, ca = labels.nc, (NHIDDEN if has_a else 0)
+    ld = ca + (32 if has_t else 0)
+    cat, actv_low = new(n, h, w, ld), None
+    cat_amax = amax_slot()     # max |cat|, written by the kernel that produces the embedding (>= 1: one-hot channels)
+    if has_a:
+        tab = new(9, nc, NHIDDEN)
+        L.call("onehot_conv3x3_pack", w_sh.contiguous(), tab, NHIDDEN, nc)
+        if cat_ups:
+            assert not has_t and ld == NHIDDEN
+            actv_low = new(n, h >> cat_ups, w >> cat_ups, NHIDDEN)
+            L.call("onehot_conv3x3_fwd", labels.t, tab, b_sh, actv_low, n, labels.h, labels.w, shift, nc, NHIDDEN,
+                   NHIDDEN, 0, 1, -1, cat_amax, 0.0)   # (the nearest upsample below keeps the maximum)
+            L.call("upsample_noise_fwd", actv_low, None, None, cat, n, h, w, NHIDDEN, cat_ups)
+        else:
+            # ... and, with a style table, the 32 one-hot label channels behind the embedding in the same launch
+            L.call("onehot_conv3x3_fwd", labels.t, tab, b_sh, cat, n, labels.h, labels.w, shift, nc, NHIDDEN, ld, 0,
+                   1, ca if has_t else -1, cat_amax, 1.0 if has_t else 0.0)
+    elif has_t:
+        L.call("label_onehot", labels.t, cat, n, labels.h, labels.w, shift, ld, ca)
+        cat_amax = None
+    return cat, cat_amax, actv_low
+
+
+def _norm_u(w2a, table, nb, rows, ca, kp, split):
+    """(U, amax) of the gamma/beta convolution for `nb` images: the shared weights w2a alone, or per image with the rows of
+    `table` (the style half over the one-hot channels) behind them"""
+    if table is None:
+        return _wino_u(w2a, rows, ca, False, rows, kp, split)
+    ua = weight_amax(w2a, table) if split >= 2 else None
+    u = _i16(36 * nb * rows * kp * {1: 3, 2: 2, 3: 1, 4: 1}[split]) if split else new(36, nb, rows, kp)
+    L.call("wino43_weights_table", w2a, table, u, nb, rows, ca, int(split), ua)
+    return u, ua
+
+
+def _norm_keeps_v(scale, nb, n, ld, rows):
+    """The V of `cat` is the Q operand of the weight / table gradient: kept for a backward pass that takes it whole"""
+    return P().keep_v and scale is not None and nb == n and _wgrad_mode(ld, rows) == 2
+
+
+def _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one, rows, nb):
+    """round 3: gamma/beta GEMM + output transform + normalise + modulate + LeakyReLU in ONE kernel (spade_fused.hip): the
+    Winograd-domain product M never reaches HBM.  Returns (kept V, max |xhat|, sign mask, max |cat|)."""
+    (n, h, w, c), ld, sg = x.shape, cat.shape[3], stat_groups(mean)
+    kp, t = L.kpad(1, 1, ld), n * (h // 4) * (w // 4)
+    ac = cat_amax if cat_amax is not None else tensor_amax(cat)
+    pk = P().half       # 16-bit storage mode: packed one-term operands, one MFMA product (dsee_spade_fused_fwd_f16p)
+    v2 = WinoOperand(_i16(36 * t * ld * (1 if pk else 2)), ac, F16P if pk else F16X2)
+    L.call("wino43_input_f16p" if pk else "wino43_input_f16x2", cat, v2.data, n, h, w, ld, ac, FUSED_V_BOUND)
+    u, ua = _norm_u(w2a, table, n, rows, ca, kp, 4 if pk else 2)
+    if PROFILE is not None:
+        global PROFILE_OPERAND_GB
+        PROFILE_OPERAND_GB += (t // 64) * (rows // 64) * 36 * 2 * 64 * ld * 4.0 / 1e9
+    with _timed("spade_fused_fwd", 2.0 * 36 * t * ld * rows,
+                4.0 * 36 * t * ld + 4.0 * n * h * w * c * (3 if scale is not None else 2)):
+        hm = amax_slot()     # max |h|: the convolution that consumes h writes its V pre-split with this bound
+        xm = amax_slot() if scale is not None else None     # max |xhat|: bounds the backward pass's gamma/beta gradient
+        # the LeakyReLU branch of h as bits: all the backward pass needs of h (1/32 of its bytes, read twice).  (The kernel forms
+        # the mask index with a shift: a channel count that is not a power of two -- ngf = 24, 48 -- keeps the backward on `out`)
+        smask = (torch.empty(n * h * w * (c // 32), dtype=torch.int32, device=x.device)
+                 if (scale is not None and P().sign_mask and (c & (c - 1)) == 0) else None)
+        # (the one-wave-per-SIMD kernel takes BatchNorm statistics only: InstanceNorm layers stay on spade_fused_fwd)
+        _call_sg("spade_fused_fwd_f16p" if pk else ("spade_fused_fwd_w4" if (P().fused_w4 and sg == 1) else
+                                                    "spade_fused_fwd"), sg,
+                 (v2.data, u, ac, FUSED_V_BOUND, ua, b2.contiguous(), x, mean, invstd, out, scale, n,
+                  h, w, c, rows, ld, n if table is not None else 1), (float(add_one), LRELU_SLOPE, hm, xm, smask))
+        tag_amax(out, hm)
+    # the weight / table gradient reads the split V the kernel above consumed, or an fp32 V of its own as its Q operand
+    keep = v2 if _norm_keeps_v(scale, nb, n, ld, rows) else None
+    if keep is not None and not P().presplit_a:
+        keep = WinoOperand(new(36, t, ld), amax_slot(), FP32)
+        L.call("wino43_input", cat, keep.data, n, h, w, ld, keep.amax)
+    return keep, xm, smask, ac       # (max |cat|: the backward's mlp_shared weight gradient takes `cat` as an operand again)
+
+
+def _norm_product_wino(cat, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one, rows, nb):
+    """The gamma/beta GEMM in the Winograd domain, chunk by chunk, then dsee_wino43_output_modulate.  Returns the kept V."""
+    (n, h, w, c), ld, sg = x.shape, cat.shape[3], stat_groups(mean)
+    kp, b2c, split = L.kpad(1, 1, ld), b2.contiguous(), _split_kind(ld, rows)
+    keep = [] if _norm_keeps_v(scale, nb, n, ld, rows) else None
+    for n0 in range(0, n, nb):
+        u, ua = _norm_u(w2a, None if table is None else table[n0:n0 + nb], nb, rows, ca, kp, split)
+        m, ms = _wino_vgemm(cat[n0:n0 + nb], nb, h, w, ld, u, rows, rows, kp, table is not None, split, keep, ua)
+        px = nb * h * w
+        with _timed("spade_modulate_fused", 0.0,
+                    (2.0 if split == 3 else 4.0) * 36 * (px // 16) * rows + 4.0 * px * c * (3 if scale is not None else 2)):
+            # (InstanceNorm: the statistics rows of this pass's images)
+            mc, ic = (mean, invstd) if sg == 1 else (mean[n0:n0 + nb], invstd[n0:n0 + nb])
+            _call_sg("wino43_output_modulate", 1 if sg == 1 else nb,
+                     (m, b2c, x[n0:n0 + nb], mc, ic, out[n0:n0 + nb], scale[n0:n0 + nb] if scale is not None else None, nb, h,
+                      w, c, rows), (float(add_one), LRELU_SLOPE, ms))
+    return keep[0] if keep else None
+
+
+def _norm_product(cat, cat_amax, w2a, table, b2, x, mean, invstd, out, scale, add_one, geom, nb, fused):
+    """out (and scale, where the backward pass will want it) on the kernel path the shapes allow.  Returns (kept V of cat, max
+    |xhat|, sign mask of out, max |cat|): what the backward pass reads besides the tensors; None where the path has none."""
+    rows, ca = geom.Cout, geom.Cin - (32 if table is not None else 0)     # ca: embedding channels in front of the one-hot ones
+    if fused:
+        return _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one, rows, nb)
+    if nb:
+        return _norm_product_wino(cat, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one, rows, nb), None, None, None
+    _norm_product_direct(geom, cat, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one)
+    return None, None, None, None
+
+
+def _norm_wino_wgrad(cat, dgb, dm_all, vcat, w_for_dx, nc, nb, has_a, has_t, rows):
+    """(dw2a, dtable, dactv): weight gradient of the gamma/beta convolution in the Winograd domain -- groups (xi, image), shared
+    columns summed over images into dw2a, one-hot columns per image into dtable -- from the gamma/beta gradient dgb or, where the
+    norm backward wrote it, its dM `dm_all`.  `w_for_dx` (w2a): also the embedding's data gradient dactv, from the same dM."""
+    n, h, w, ld = cat.shape
+    dw2a = dactv = None
+    t, ca, mode, with_dx = nb * (h // 4) * (w // 4), (NHIDDEN if has_a else 0), _wgrad_mode(ld, rows), w_for_dx is not None
+    if with_dx:
+        rows_t = L.wrows(NHIDDEN)
+        u_t = _wino_u(w_for_dx, rows, NHIDDEN, 2, rows_t, L.kpad(1, 1, rows),
+                      4 if (dm_all is not None and dm_all.form == F16P) else _split_kind(rows, NHIDDEN))
+        dactv = new(n, h, w, NHIDDEN) if nb != n else None
+    nbytes = (L.lib().dsee_wino43_wgrad_table_workspace(C.c_long(t), nb, ca, rows) if has_t else
+              L.lib().dsee_wino43_wgrad_workspace(C.c_long(t), ld, rows))
+    dtable = new(n, 9, rows, 32) if has_t else None
+    wsw = scratch(nbytes, "wgrad")
+    for n0 in range(0, n, nb):
+        v, dm = _wino_wgrad_operands(cat[n0:n0 + nb], None if dm_all is not None else dgb[n0:n0 + nb], nb, h, w, ld, rows,
+                                     mode, vcat if (mode == 2 and nb == n) else None, dm_all)
+        dwc = new(rows, NHIDDEN, 3, 3) if has_a else None
+        tail = (_wgrad_code(v, dm, mode), v.amax, dm.amax)
+        with _timed(_wgrad_name(mode), 2.0 * 36 * t * ld * rows):
+            if has_t:
+                L.call("wino43_wgrad_table", v.data, dm.data, wsw, nbytes, dwc, dtable[n0:n0 + nb], t, nb, ca, rows, nc, *tail)
+            else:
+                L.call("wino43_wgrad", v.data, dm.data, wsw, nbytes, dwc, t, ld, rows, rows, NHIDDEN, *tail)
+        if dwc is not None:
+            dw2a = dwc if dw2a is None else dw2a.add_(dwc)
+        if with_dx:
+            # (the ReLU mask of the embedding rides in the epilogue when the one-hot channels share `cat`)
+            dac = _wino_dgrad_from_dm(dm, u_t, nb, h, w, rows, NHIDDEN, rows_t,
+                                      cat[n0:n0 + nb] if has_t else None, ld if has_t else 0)
+            if nb == n:
+                dactv = dac
+            else:
+                dactv[n0:n0 + nb].copy_(dac)
+    return dw2a, dtable, dactv
+
+
+def _embedding_dgrad(dgb, w2a, cat, rows, has_t, wino):
+    """dactv: data gradient w.r.t. the 128 embedding channels only (the one-hot channels need none), by a pass of its own over
+    the gamma/beta gradient dgb.  With the one-hot channels in `cat` (`has_t`) the ReLU backward is fused into the epilogue."""
+    n, h, w, ld = cat.shape
+    res, act, res_ld = (cat, L.ACT_MASK, ld) if has_t else (None, L.ACT_NONE, 0)
+    if wino and _wino_chunk(n, h, w, rows) is not None:
+        return _wino_conv(dgb, w2a, n, h, w, NHIDDEN, rows, True, None, res, act, res_ld=res_ld)
+    ga = L.ConvGeom(n, h, w, rows, h, w, NHIDDEN, 3, 3, 1, 1, -1, 0, 0, 1)
+    return conv_raw(dgb, _pack_dgrad(w2a, rows, 1), ga, None, res, act, res_ld=res_ld)
+
+
+def _mlp_shared_grad(dactv, cat, cat_amax, actv_low, cat_ups, lab, shift, has_t):
+    """(dw_sh, db_sh) of mlp_shared, a 3x3 convolution over the one-hot label, from the embedding's gradient dactv."""
+    n, h, w, ld = cat.shape
+    if has_t:
+        # (ReLU backward done in the dgrad epilogue) the weight gradient w.r.t. the one-hot channels already sitting in `cat`
+        # (MFMA); known: the operand maximum the forward pass already wrote
+        known = {(cat.data_ptr(), cat.numel(), cat._version): cat_amax} if cat_amax is not None else {}
+        dw_sh = wgrad_raw(cat, dactv, L.geom_fwd(n, h, w, ld, NHIDDEN, 3, 1, 1, 0), NHIDDEN, lab.nc, 3, 3, cin_first=NHIDDEN,
+                          amax_cache=known)
+        return dw_sh, channel_dot(dactv, None, NHIDDEN).clone()
+    wso = scratch(L.lib().dsee_onehot_conv3x3_wgrad_workspace(n, lab.h, lab.w, shift, lab.nc), "ohw")
+    act_lo, ld_lo = cat, ld
+    if cat_ups:
+        # gradient of the nearest upsample: 2^ups x 2^ups block sums; the ReLU mask is constant per block
+        dlow = torch.empty_like(actv_low)
+        L.call("sumpool", dactv, dlow, n, h, w, NHIDDEN, cat_ups)
+        dactv, act_lo, ld_lo = dlow, actv_low, NHIDDEN
+    if P().onehot_wgrad_mfma and ld_lo == NHIDDEN and _direct_split_on():
+        # round 6: the compare-select kernel is VALU bound (128 channels x 9 taps x 20 labels per pixel: 0.29 ms at 64^2,
+        # N = 8); the MFMA weight gradient over 32 materialised one-hot channels takes 0.07 (profiles/r06_onehot_wgrad.txt)
+        g1 = torch.empty_like(dactv)
+        tag_amax(g1, amax_slot())
+        L.call("act_bwd_amax", dactv.contiguous(), act_lo, g1, C.c_long(g1.numel()), L.ACT_RELU, LRELU_SLOPE, g1.dsee_amax)
+        oh = new(*g1.shape[:3], MAX_LABELS)     # (lab.nc <= MAX_LABELS: Labels checks it where the map is built)
+        L.call("label_onehot", lab.t, oh, n, lab.h, lab.w, shift, 32, 0)
+        dw_sh = wgrad_raw(oh, g1, L.geom_fwd(*g1.shape[:3], 32, NHIDDEN, 3, 1, 1, 0), NHIDDEN, lab.nc, 3, 3)
+        return dw_sh, channel_dot(g1, None, NHIDDEN).clone()
+    dw_sh, db_sh = new(NHIDDEN, lab.nc, 3, 3), new(NHIDDEN)
+    L.call("onehot_conv3x3_wgrad", lab.t, dactv, NHIDDEN, act_lo, ld_lo, n, lab.h, lab.w, shift, lab.nc, dw_sh, db_sh, wso)
+    return dw_sh, db_sh
+
+
 class SeanNormTable(torch.autograd.Function):
     """SPADE / SEAN / PureSEAN norm + LeakyReLU as ONE node, with the SEAN style half as per-image tables.
 
@@ -1971,6 +2154,7 @@ class SeanNormTable(torch.autograd.Function):
     [ReLU(mlp_shared(seg)) (128) ; one-hot label (19 -> 32)] = 160 channels (K = 1440) instead of
     [actv ; style_map] = 256 (K = 2304), and the style gradient is a label-segmented sum of the gamma/beta
     gradient rows.  `table` None -> SPADE (128 channels); `w2a` None -> PureSEAN (one-hot only)."""
+    W2A, B2 = 3, 5      # positions of w2a and b2 in forward's arguments (ctx.needs_input_grad)
 
     @staticmethod
     def forward(ctx, x, *args):
@@ -1988,37 +2172,14 @@ class SeanNormTable(torch.autograd.Function):
         resolution before the gamma/beta convolution; there is no style table then."""
         ctx.grad_sink = grad_sink
         n, h, w, c = x.shape
-        nc = labels.nc
         has_a, has_t = w2a is not None, table is not None
         rows = w2a.shape[0] if has_a else table.shape[2]
-        ca = NHIDDEN if has_a else 0
-        ld = ca + (32 if has_t else 0)
-        cat = new(n, h, w, ld)
-        actv_low = None
-        cat_amax = amax_slot()     # max |cat|, written by the kernel that produces the embedding (>= 1: one-hot channels)
-        if has_a:
-            tab = new(9, nc, NHIDDEN)
-            L.call("onehot_conv3x3_pack", w_sh.contiguous(), tab, NHIDDEN, nc)
-            if cat_ups:
-                assert not has_t and ld == NHIDDEN
-                actv_low = new(n, h >> cat_ups, w >> cat_ups, NHIDDEN)
-                L.call("onehot_conv3x3_fwd", labels.t, tab, b_sh, actv_low, n, labels.h, labels.w, shift, nc, NHIDDEN,
-                       NHIDDEN, 0, 1, -1, cat_amax, 0.0)   # (the nearest upsample below keeps the maximum)
-                L.call("upsample_noise_fwd", actv_low, None, None, cat, n, h, w, NHIDDEN, cat_ups)
-            else:
-                # ... and, with a style table, the 32 one-hot label channels behind the embedding in the same launch
-                L.call("onehot_conv3x3_fwd", labels.t, tab, b_sh, cat, n, labels.h, labels.w, shift, nc, NHIDDEN, ld, 0,
-                       1, ca if has_t else -1, cat_amax, 1.0 if has_t else 0.0)
-        elif has_t:
-            L.call("label_onehot", labels.t, cat, n, labels.h, labels.w, shift, ld, ca)
-            cat_amax = None
+        cat, cat_amax, actv_low = _norm_cat(w_sh, b_sh, labels, shift, n, h, w, has_a, has_t, cat_ups)
+        ld = cat.shape[3]
         mean, invstd, ctx.sync = norm_stats(x, running_mean, running_var, training)
-        sg = stat_groups(mean)
         geom = L.geom_fwd(n, h, w, ld, rows, 3, 1, 1, 0)
         assert geom.korder == 1
-        if has_a:
-            w2a = w2a.contiguous()
-        tb = table.contiguous() if has_t else None
+        w2a, tb = (w2a.contiguous() if has_a else None), (table.contiguous() if has_t else None)
         nb = ctx.wino_nb = _wino_mod_chunk(n, h, w, c, rows, has_t)
         # `scale` is only read by the backward pass: the no-grad generator forward of the D step does not write it
         need_scale = any(ctx.needs_input_grad) or not nb
@@ -2026,208 +2187,46 @@ class SeanNormTable(torch.autograd.Function):
         # (16-bit storage mode: the fused kernel writes the modulation factor as fp16 -- the backward pass is its only reader)
         sdt = torch.float16 if (fused and P().half) else torch.float32
         out, scale = torch.empty_like(x), (torch.empty(x.shape, dtype=sdt, device=x.device) if need_scale else None)
-        if fused:
-            # round 3: gamma/beta GEMM + output transform + normalise + modulate + LeakyReLU in ONE kernel
-            # (spade_fused.hip): the Winograd-domain product M never reaches HBM
-            kp = L.kpad(1, 1, ld)
-            t = n * (h // 4) * (w // 4)
-            ac = cat_amax if cat_amax is not None else tensor_amax(cat)
-            pk = P().half       # 16-bit storage mode: packed one-term operands, one MFMA product (dsee_spade_fused_fwd_f16p)
-            sp = 4 if pk else 2
-            v2 = _i16(36 * t * ld * (1 if pk else 2))
-            L.call("wino43_input_f16p" if pk else "wino43_input_f16x2", cat, v2, n, h, w, ld, ac, FUSED_V_BOUND)
-            if has_t:
-                ua = weight_amax(w2a if has_a else None, tb)
-                u = _i16(36 * n * rows * kp * (1 if pk else 2))
-                L.call("wino43_weights_table", w2a if has_a else None, tb, u, n, rows, ca, sp, ua)
-            else:
-                u, ua = _wino_u(w2a, rows, ca, False, rows, kp, sp)
-            if PROFILE is not None:
-                global PROFILE_OPERAND_GB
-                PROFILE_OPERAND_GB += (t // 64) * (rows // 64) * 36 * 2 * 64 * ld * 4.0 / 1e9
-            with _timed("spade_fused_fwd", 2.0 * 36 * t * ld * rows,
-                        4.0 * 36 * t * ld + 4.0 * n * h * w * c * (3 if need_scale else 2)):
-                hm = amax_slot()     # max |h|: the convolution that consumes h writes its V pre-split with this bound
-                xm = amax_slot() if need_scale else None     # max |xhat|: bounds the backward pass's gamma/beta gradient
-                # the LeakyReLU branch of h as bits: all the backward pass needs of h (1/32 of its bytes, read twice)
-                # (the kernel forms the mask index with a shift: a channel count that is not a power of two -- ngf = 24, 48 --
-                # keeps the backward pass on `out`)
-                smask = (torch.empty(n * h * w * (c // 32), dtype=torch.int32, device=x.device)
-                         if (need_scale and P().sign_mask and (c & (c - 1)) == 0) else None)
-                # (the one-wave-per-SIMD kernel takes BatchNorm statistics only: InstanceNorm layers stay on spade_fused_fwd)
-                _call_sg("spade_fused_fwd_f16p" if pk else ("spade_fused_fwd_w4" if (P().fused_w4 and sg == 1) else
-                                                            "spade_fused_fwd"), sg,
-                         (v2, u, ac, FUSED_V_BOUND, ua, b2.contiguous(), x, mean, invstd, out, scale if need_scale else None, n,
-                          h, w, c, rows, ld, n if has_t else 1), (float(add_one), LRELU_SLOPE, hm, xm, smask))
-                tag_amax(out, hm)
-                ctx.xhat_amax = xm
-                ctx.sign_mask = smask
-                ctx.cat_amax = ac        # (max |cat|: the backward's mlp_shared weight gradient takes `cat` as an operand again)
-            keep = None
-            if P().keep_v and need_scale and nb == n and _wgrad_mode(ld, rows) == 2:
-                if P().presplit_a:
-                    keep = [(v2, ac, "pk" if pk else True)]     # the weight / table gradient reads the split V the kernel above consumed
-                else:
-                    # ... or an fp32 V of its own as its Q operand
-                    vq = (new(36, t, ld), amax_slot())
-                    L.call("wino43_input", cat, vq[0], n, h, w, ld, vq[1])
-                    keep = [vq]
-        elif nb:
-            tpi = (h // 4) * (w // 4)
-            kp = L.kpad(1, 1, ld)
-            b2c = b2.contiguous()
-            split = _split_kind(ld, rows)
-            # the fp32 V of `cat` is the Q operand of the weight / table gradient: kept for the backward pass
-            keep = [] if (P().keep_v and need_scale and nb == n and _wgrad_mode(ld, rows) == 2) else None
-            for n0 in range(0, n, nb):
-                if has_t:
-                    ua = weight_amax(w2a if has_a else None, tb[n0:n0 + nb]) if split >= 2 else None
-                    u = _i16(36 * nb * rows * kp * {1: 3, 2: 2, 3: 1}[split]) if split else new(36, nb, rows, kp)
-                    L.call("wino43_weights_table", w2a if has_a else None, tb[n0:n0 + nb], u, nb, rows, ca, int(split),
-                           ua)
-                else:
-                    u, ua = _wino_u(w2a, rows, ca, False, rows, kp, split)
-                m, ms = _wino_vgemm(cat[n0:n0 + nb], nb, h, w, ld, u, rows, rows, kp, has_t, split, keep, ua)
-                px = nb * h * w
-                with _timed("spade_modulate_fused", 0.0,
-                            (2.0 if split == 3 else 4.0) * 36 * (px // 16) * rows
-                            + 4.0 * px * c * (3 if need_scale else 2)):
-                    # (InstanceNorm: the statistics rows of this pass's images)
-                    mc, ic = (mean, invstd) if sg == 1 else (mean[n0:n0 + nb], invstd[n0:n0 + nb])
-                    _call_sg("wino43_output_modulate", 1 if sg == 1 else nb,
-                             (m, b2c, x[n0:n0 + nb], mc, ic, out[n0:n0 + nb], scale[n0:n0 + nb] if need_scale else None, nb, h,
-                              w, c, rows), (float(add_one), LRELU_SLOPE, ms))
-        else:
-            wp = _pack_fwd(w2a, ca, 1) if has_a else None
-            with _timed(_variant(geom, True), _flops(geom)):
-                _call_sg("conv2d_modulate_fwd", sg, (C.byref(geom), cat, wp, tb, ca, b2.contiguous(), x, mean, invstd, out,
-                                                      scale, c), (float(add_one), LRELU_SLOPE))
+        vcat, ctx.xhat_amax, ctx.sign_mask, ctx.cat_amax = _norm_product(cat, cat_amax, w2a, tb, b2, x, mean, invstd, out, scale,
+                                                                          add_one, geom, nb, fused)
         ctx.geom, ctx.labels, ctx.shift, ctx.has_a, ctx.has_t, ctx.rows = geom, labels, shift, has_a, has_t, rows
-        ctx.cat_ups = cat_ups
-        vcat = keep[0] if (nb and keep) else (None, None)
-        ctx.v_kind = vcat[2] if len(vcat) == 3 else None
-        ctx.w_amax = getattr(w2a, "dsee_amax", None) if has_a else None
-        ctx.save_for_backward(x, cat, w2a if has_a else None, out, scale, mean, invstd, *vcat[:2], actv_low)
+        ctx.cat_ups, ctx.w_amax = cat_ups, (getattr(w2a, "dsee_amax", None) if has_a else None)
+        save_with_operand(ctx, vcat, x, cat, w2a, out, scale, mean, invstd, actv_low)
         return out
 
     @staticmethod
     @_under_plan
     def backward(ctx, dh):
-        x, cat, w2a, out, scale, mean, invstd, vc, vc_amax, actv_low = ctx.saved_tensors
+        (x, cat, w2a, out, scale, mean, invstd, actv_low), vcat = saved_with_operand(ctx)
         if w2a is not None:
             w2a.dsee_amax = ctx.w_amax     # (an upper bound: the slot also holds max |style table|)
-        vcat = ((vc, vc_amax, ctx.v_kind) if ctx.v_kind else (vc, vc_amax)) if vc is not None else None
-        geom, lab, shift, rows = ctx.geom, ctx.labels, ctx.shift, ctx.rows
-        n, h, w, c = x.shape
-        ld = cat.shape[3]
-        dw_sh = db_sh = dw2a = dtable = db2 = None
-        nb = ctx.wino_nb
-        wino_w = bool(nb) and (ctx.has_t or ctx.needs_input_grad[3])
+        geom, lab, rows, nb = ctx.geom, ctx.labels, ctx.rows, ctx.wino_nb
+        (n, h, w, c), ld = x.shape, cat.shape[3]
+        dw_sh = db_sh = dw2a = dtable = db2 = dactv = None
+        mode = _wgrad_mode(ld, rows)
+        wino_w = bool(nb) and (ctx.has_t or ctx.needs_input_grad[SeanNormTable.W2A])
         # the embedding's data gradient from the weight gradient's dM (adjoint form): no second transform of the
         # 1024-channel gamma/beta gradient
-        fused_d = (wino_w and ctx.has_a and _wgrad_mode(ld, rows) != 1 and _adjoint_ok(rows, NHIDDEN))
-        dactv_fused = [None]
+        fused_d = wino_w and ctx.has_a and mode != 1 and _adjoint_ok(rows, NHIDDEN)
         # every consumer of the gamma/beta gradient reads dM: let the norm backward write it directly
-        as_dm = (P().fuse_dm and wino_w and nb == n and _wgrad_mode(ld, rows) != 1 and (fused_d or not ctx.has_a)
-                 and 256 % (c // 4) == 0)
+        as_dm = P().fuse_dm and wino_w and nb == n and mode != 1 and (fused_d or not ctx.has_a) and 256 % (c // 4) == 0
         add = ctx.grad_sink.take() if ctx.grad_sink is not None else None
         # (pre-split dM needs both of its consumers on the pre-split kernels: the TN weight gradient reads the kept V2, the
         # adjoint GEMM takes 256-row tiles)
-        pre_ok = vcat is not None and len(vcat) == 3 and _wgrad_mode(ld, rows) == 2 and (not ctx.has_a or fused_d)
+        pre_ok = vcat is not None and vcat.form in (F16X2, F16P) and mode == 2 and (not ctx.has_a or fused_d)
         dx, dgb, cs, dm_all = modulate_bwd(dh, out, x, scale, mean, invstd, rows, ctx.sync, as_dm, add,
-                                           getattr(ctx, "xhat_amax", None) if pre_ok else None,
-                                           getattr(ctx, "sign_mask", None))
-
-        def wino_wgrad():
-            dw2a = dtable = None
-            # weight gradient in the Winograd domain: groups (xi, image), shared columns summed over images
-            tpi, ca = (h // 4) * (w // 4), (NHIDDEN if ctx.has_a else 0)
-            if fused_d:
-                rows_t = L.wrows(NHIDDEN)
-                u_t = _wino_u(w2a, rows, NHIDDEN, 2, rows_t, L.kpad(1, 1, rows),
-                              4 if _is_pk(dm_all) else _split_kind(rows, NHIDDEN))
-                dactv_fused[0] = new(n, h, w, NHIDDEN) if nb != n else None
-            if ctx.has_t:
-                nbytes = L.lib().dsee_wino43_wgrad_table_workspace(C.c_long(nb * tpi), nb, ca, rows)
-                dtable = new(n, 9, rows, 32)
-            else:
-                nbytes = L.lib().dsee_wino43_wgrad_workspace(C.c_long(nb * tpi), ld, rows)
-            wsw = scratch(nbytes, "wgrad")
-            mode = _wgrad_mode(ld, rows)
-            for n0 in range(0, n, nb):
-                v, dm = _wino_wgrad_operands(cat[n0:n0 + nb], None if as_dm else dgb[n0:n0 + nb], nb, h, w, ld, rows,
-                                             mode, vcat if (mode == 2 and nb == n) else None, dm_all)
-                dwc = new(rows, NHIDDEN, 3, 3) if ctx.has_a else None
-                with _timed(_wgrad_name(mode), 2.0 * 36 * nb * tpi * ld * rows):
-                    if ctx.has_t:
-                        L.call("wino43_wgrad_table", v[0], dm[0], wsw, nbytes, dwc, dtable[n0:n0 + nb], nb * tpi, nb, ca,
-                               rows, lab.nc, _wgrad_code(v, dm, mode), v[1], dm[1])
-                    else:
-                        L.call("wino43_wgrad", v[0], dm[0], wsw, nbytes, dwc, nb * tpi, ld, rows, rows, NHIDDEN,
-                               _wgrad_code(v, dm, mode), v[1], dm[1])
-                if dwc is not None:
-                    dw2a = dwc if dw2a is None else dw2a.add_(dwc)
-                if fused_d:
-                    # (the ReLU mask of the embedding rides in the epilogue when the one-hot channels share `cat`)
-                    dac = _wino_dgrad_from_dm(dm, u_t, nb, h, w, rows, NHIDDEN, rows_t,
-                                              cat[n0:n0 + nb] if ctx.has_t else None, ld if ctx.has_t else 0)
-                    if nb == n:
-                        dactv_fused[0] = dac
-                    else:
-                        dactv_fused[0][n0:n0 + nb].copy_(dac)
-            return dw2a, dtable
-
+                                           ctx.xhat_amax if pre_ok else None, ctx.sign_mask)
+        # (the weight gradient runs before the embedding block when that block takes its dactv, after it otherwise)
+        wino_args = (cat, dgb, dm_all, vcat, w2a if fused_d else None, lab.nc, nb, ctx.has_a, ctx.has_t, rows)
         if fused_d:
-            dw2a, dtable = wino_wgrad()
+            dw2a, dtable, dactv = _norm_wino_wgrad(*wino_args)
         if ctx.has_a:
-            # data gradient only w.r.t. the 128 embedding channels (the one-hot channels need none)
-            ga = L.ConvGeom(n, h, w, rows, h, w, NHIDDEN, 3, 3, 1, 1, -1, 0, 0, 1)
-            wino_d = ctx.wino_nb and _wino_chunk(n, h, w, rows) is not None
-            if ctx.has_t:
-                # ReLU backward fused into the dgrad epilogue; the gradient of mlp_shared (a conv over the one-hot
-                # label) is then the weight gradient w.r.t. the one-hot channels already sitting in `cat` (MFMA)
-                if fused_d:
-                    dactv = dactv_fused[0]
-                elif wino_d:
-                    dactv = _wino_conv(dgb, w2a, n, h, w, NHIDDEN, rows, True, None, cat, L.ACT_MASK, res_ld=ld)
-                else:
-                    dactv = conv_raw(dgb, _pack_dgrad(w2a, rows, 1), ga, None, cat, L.ACT_MASK, res_ld=ld)
-                gs = L.geom_fwd(n, h, w, ld, NHIDDEN, 3, 1, 1, 0)
-                known = {}          # operand maxima the forward pass / the producer of dactv already wrote
-                if getattr(ctx, "cat_amax", None) is not None:
-                    known[(cat.data_ptr(), cat.numel(), cat._version)] = ctx.cat_amax
-                dw_sh = wgrad_raw(cat, dactv, gs, NHIDDEN, lab.nc, 3, 3, cin_first=NHIDDEN, amax_cache=known)
-                db_sh = channel_dot(dactv, None, NHIDDEN).clone()
-            else:
-                dactv = (dactv_fused[0] if fused_d else
-                         _wino_conv(dgb, w2a, n, h, w, NHIDDEN, rows, True) if wino_d
-                         else conv_raw(dgb, _pack_dgrad(w2a, rows, 1), ga))
-                dw_sh, db_sh = new(NHIDDEN, lab.nc, 3, 3), new(NHIDDEN)
-                wso = scratch(L.lib().dsee_onehot_conv3x3_wgrad_workspace(n, lab.h, lab.w, shift, lab.nc), "ohw")
-                act_lo, ld_lo = cat, ld
-                if ctx.cat_ups:
-                    # gradient of the nearest upsample: 2^ups x 2^ups block sums; the ReLU mask is constant per block
-                    dlow = torch.empty_like(actv_low)
-                    L.call("sumpool", dactv, dlow, n, h, w, NHIDDEN, ctx.cat_ups)
-                    dactv, act_lo, ld_lo = dlow, actv_low, NHIDDEN
-                if P().onehot_wgrad_mfma and ld_lo == NHIDDEN and _direct_split_on():
-                    # round 6: the compare-select kernel is VALU bound (128 channels x 9 taps x 20 labels per pixel: 0.29 ms at 64^2,
-                    # N = 8); the MFMA weight gradient over 32 materialised one-hot channels takes 0.07 (profiles/r06_onehot_wgrad.txt)
-                    rh, rw_ = dactv.shape[1], dactv.shape[2]
-                    g1 = torch.empty_like(dactv)
-                    tag_amax(g1, amax_slot())
-                    L.call("act_bwd_amax", dactv.contiguous(), act_lo, g1, C.c_long(g1.numel()), L.ACT_RELU, LRELU_SLOPE, g1.dsee_amax)
-                    oh = new(n, rh, rw_, MAX_LABELS)     # (lab.nc <= MAX_LABELS: Labels checks it where the map is built)
-                    L.call("label_onehot", lab.t, oh, n, lab.h, lab.w, shift, 32, 0)
-                    dw_sh = wgrad_raw(oh, g1, L.geom_fwd(n, rh, rw_, 32, NHIDDEN, 3, 1, 1, 0), NHIDDEN, lab.nc, 3, 3)
-                    db_sh = channel_dot(g1, None, NHIDDEN).clone()
-                else:
-                    L.call("onehot_conv3x3_wgrad", lab.t, dactv, NHIDDEN, act_lo, ld_lo, n, lab.h, lab.w, shift, lab.nc,
-                           dw_sh, db_sh, wso)
-        if wino_w and not fused_d:
-            dw2a, dtable = wino_wgrad()
+            if not fused_d:
+                dactv = _embedding_dgrad(dgb, w2a, cat, rows, ctx.has_t, bool(nb))
+            dw_sh, db_sh = _mlp_shared_grad(dactv, cat, ctx.cat_amax, actv_low, ctx.cat_ups, lab, ctx.shift, ctx.has_t)
         if wino_w:
-            pass
+            if not fused_d:
+                dw2a, dtable, _ = _norm_wino_wgrad(*wino_args)
         elif ctx.has_t:
             # one split-K launch (image-aligned splits): shared columns -> dw2a, one-hot columns per image -> dtable
             nbytes = L.lib().dsee_conv2d_wgrad_table_workspace(C.byref(geom))
@@ -2238,11 +2237,10 @@ class SeanNormTable(torch.autograd.Function):
             with _timed("conv_wgrad_128x128(+slab reduce)", _flops(geom)):
                 L.call("conv2d_wgrad_table", C.byref(geom), cat, dgb, wsw, C.c_size_t(nbytes), dw2a, ld - 32, dtable,
                        lab.nc)
-        elif ctx.has_a and ctx.needs_input_grad[3]:
+        elif ctx.has_a and ctx.needs_input_grad[SeanNormTable.W2A]:
             dw2a = wgrad_raw(cat, dgb, geom, rows, NHIDDEN, 3, 3)
-        if ctx.needs_input_grad[5]:
-            idx, _ = packed_perm(c, x.device)
-            db2 = torch.cat([cs.reshape(-1), torch.zeros(1, device=x.device)]).index_select(0, idx)
+        if ctx.needs_input_grad[SeanNormTable.B2]:
+            db2 = _packed_bias_grad(cs, c)
         return dx, dw_sh, db_sh, dw2a, dtable, db2, None, None, None, None, None, None, None, None
 
 

@@ -690,3 +690,68 @@ def test_kernel_plan_is_per_model_and_per_thread():
     with b.active():
         y.sum().backward()
     assert seen == [a]
+
+
+def test_wgrad_code_table_matches_the_tuple_encoding_it_replaced():
+    """ops._wgrad_code on (V form, dM form, mode) gives the `split` argument of dsee_wino43_wgrad[_table] that the tuple
+    encoding gave -- (t, amax) fp32 or transposed bf16x3, (t, amax, True) fp16x2, (t, amax, "pk") packed -- for every pairing
+    that encoding could produce, under the plans that change _wgrad_split; any other pairing raises."""
+    from deepsee_amd import ops, plan as PL
+    from deepsee_amd.options import make_opt
+
+    def old_code(v, dm, mode):         # the function as it stood on tuples
+        pk = lambda o: len(o) == 3 and o[2] == "pk"
+        if pk(v):
+            assert pk(dm)
+            return 7
+        if len(v) == 3:
+            return 6 if len(dm) == 3 else 5
+        return ops._wgrad_split(mode)
+
+    t = torch.zeros(1)
+    old = {ops.FP32: (t, t), ops.F16X2: (t, t, True), ops.F16P: (t, t, "pk"), ops.BF16X3_T: (t, None)}
+    legal = [(ops.FP32, ops.FP32, 0), (ops.FP32, ops.FP32, 2), (ops.BF16X3_T, ops.BF16X3_T, 1),
+             (ops.F16X2, ops.FP32, 2), (ops.F16X2, ops.F16X2, 2), (ops.F16P, ops.F16P, 2)]
+    forms = list(old)
+    plans = [PL.DEFAULT_PLAN, PL.from_opt(make_opt(kernel_plan=dict(gemm_f16x2=False))), PL.from_opt(make_opt(precision="fp16"))]
+    seen = set()
+    for plan in plans:
+        with plan.active():
+            for vf, df, mode in legal:
+                got = ops._wgrad_code(ops.WinoOperand(t, None, vf), ops.WinoOperand(t, None, df), mode)
+                assert got == old_code(old[vf], old[df], mode), (vf, df, mode)
+                seen.add(got)
+            for vf in forms:
+                for df in forms:
+                    for mode in (0, 1, 2):
+                        if (vf, df) in {(a, b) for a, b, _ in legal} and (vf == ops.BF16X3_T) == (mode == 1):
+                            continue
+                        with pytest.raises(ValueError):
+                            ops._wgrad_code(ops.WinoOperand(t, None, vf), ops.WinoOperand(t, None, df), mode)
+    assert seen == set(range(8))           # every code of the entry point was exercised
+    # the pairing the old function only asserted: a packed V with a non-packed dM
+    for df in (ops.FP32, ops.F16X2, ops.BF16X3_T):
+        with pytest.raises(ValueError):
+            ops._wgrad_code(ops.WinoOperand(t, t, ops.F16P), ops.WinoOperand(t, t, df), 2)
+
+
+def test_operand_survives_an_autograd_context():
+    """ops.save_with_operand / saved_with_operand: an operand of each form (and none) comes back from a context with the same
+    form and the same tensors, next to the other saved tensors."""
+    from deepsee_amd import ops
+
+    class Ctx:
+        def save_for_backward(self, *tensors):
+            self.saved_tensors = tensors
+
+    a, b, d, m = torch.zeros(2), None, torch.ones(3), torch.ones(1)
+    for form in (ops.FP32, ops.F16X2, ops.F16P, ops.BF16X3_T):
+        ctx = Ctx()
+        op = ops.WinoOperand(d, None if form == ops.BF16X3_T else m, form)
+        ops.save_with_operand(ctx, op, a, b)
+        assert all(t is None or isinstance(t, torch.Tensor) for t in ctx.saved_tensors)    # only tensors go through autograd
+        (ra, rb), back = ops.saved_with_operand(ctx)
+        assert ra is a and rb is None and back.form == form and back.data is d and back.amax is op.amax
+    ctx = Ctx()
+    ops.save_with_operand(ctx, None, a)
+    assert ops.saved_with_operand(ctx) == ([a], None)
