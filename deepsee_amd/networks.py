@@ -526,18 +526,56 @@ class SPADEResnetBlock(nn.Module):
                           res_sink=sink, defer_act_bwd=defer_act_bwd)
 
 
+class ResnetBlock(nn.Module):
+    """The pix2pixHD block of the netG ablation `nospadenostyle` (ablation.py:13-29) with norm_layer = spectralinstance
+    (ablation.py:147: the conv's bias removed, InstanceNorm2d(affine=False)):
+        ReflectionPad(1) -> SN conv3x3 -> IN -> ReLU -> ReflectionPad(1) -> SN conv3x3 -> IN;  out = x + y
+    State-dict keys as the reference's nn.Sequential: conv_block.{1,4}.0.{weight_orig,weight_u,weight_v}.  Labels, style and
+    noise are unused.  The reflection padding is the border pass of ops.Conv2d (`reflect`), the closing sum rides in the second
+    norm's pass (ops.InstNormRes)."""
+    kind = "resnet"
+    defers_act = False      # (the LeakyReLU in front of conv_img is applied here, forward and backward: no `in_act` contract)
+
+    def __init__(self, c):
+        super().__init__()
+        attach(self, "conv_block.1.0", SNConvP(c, c, 3, False))
+        attach(self, "conv_block.4.0", SNConvP(c, c, 3, False))
+
+    @property
+    def conv_0(self):
+        return self.conv_block._modules["1"]._modules["0"]
+
+    @property
+    def conv_1(self):
+        return self.conv_block._modules["4"]._modules["0"]
+
+    def forward(self, x, labels, style, noise, tag, ups, training, out_act=L.ACT_NONE, defer_act_bwd=False):
+        assert not defer_act_bwd
+        if ups:
+            x = ops.UpNoise.apply(x, None, None, ups)
+        h = ops.conv2d(x, self.conv_0.weight(training), None, reflect=True)
+        h = ops.InstNormAct.apply(h, L.ACT_RELU)
+        h = ops.conv2d(h, self.conv_1.weight(training), None, reflect=True)
+        return ops.InstNormRes.apply(h, x, out_act)
+
+
+def make_block(c, opt, kind):
+    """One generator block of a sr_model.block_plan kind: 'resnet' (netG = nospadenostyle) or a SPADE / SEAN / PureSEAN block."""
+    return ResnetBlock(c) if kind == "resnet" else SPADEResnetBlock(c, opt, kind)
+
+
 class DeepSEESR(nn.Module):
-    """sr.py:10-98."""
+    """sr.py:10-98; with the block kinds of sr_model.block_plan also the three generators of ablation.py (opt.netG)."""
 
     def __init__(self, opt, plan):
         super().__init__()
         c = 16 * opt.ngf
         self.c = c
         self.initial = ConvP(c, 3, 3)
-        self.head_0 = SPADEResnetBlock(c, opt, plan[0][1])
-        self.G_middle_0 = SPADEResnetBlock(c, opt, plan[1][1])
-        self.G_middle_1 = SPADEResnetBlock(c, opt, plan[2][1])
-        self.up_list = nn.ModuleList([SPADEResnetBlock(c, opt, k) for _, k in plan[3:]])
+        self.head_0 = make_block(c, opt, plan[0][1])
+        self.G_middle_0 = make_block(c, opt, plan[1][1])
+        self.G_middle_1 = make_block(c, opt, plan[2][1])
+        self.up_list = nn.ModuleList([make_block(c, opt, k) for _, k in plan[3:]])
         self.conv_img = ConvP(3, c, 3)
         self._sn = None
 
@@ -553,7 +591,7 @@ class DeepSEESR(nn.Module):
             # the LeakyReLU in front of conv_img (sr.py:94) rides in the last block's epilogue
             # ... and its BACKWARD in conv_img's data-gradient kernel (x has no other consumer): ops.Conv2d.forward
             last = i == len(blocks) - 1
-            defer = last and torch.is_grad_enabled() and x.requires_grad and ops.P().defer_act
+            defer = last and torch.is_grad_enabled() and x.requires_grad and ops.P().defer_act and getattr(blk, "defers_act", True)
             x = blk(x, labels, style, noise, tag, ups, training, L.ACT_LRELU if last else L.ACT_NONE, defer)
         return ops.conv2d(x, self.conv_img.weight, self.conv_img.bias, act=L.ACT_TANH, in_act=L.ACT_LRELU if defer else 0)
 

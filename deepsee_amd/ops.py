@@ -953,8 +953,10 @@ class Conv2d(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, res, stride, pad, ups, act, noise_w=None, noise_eps=None, res_noise_w=None,
-                res_noise_eps=None, res_sink=None, exact=False, stats=False, in_act=0, defer_act_bwd=False):
-        """`exact`: keep a direct convolution on the fp32 MFMA (no operand-maximum passes over its activations).
+                res_noise_eps=None, res_sink=None, exact=False, stats=False, in_act=0, defer_act_bwd=False, reflect=False):
+        """`reflect`: the padding is nn.ReflectionPad2d(1) instead of zeros (3 x 3, stride 1, no epilogue but the bias): the
+        zero-padded layer runs as always and dsee_reflect_ring_* add the border terms in place, here and in backward.
+        `exact`: keep a direct convolution on the fp32 MFMA (no operand-maximum passes over its activations).
         `defer_act_bwd` / `in_act` are the two halves of ONE contract set up by the caller (networks.DeepSEESR.forward): this
         layer's output y = LeakyReLU(.) has exactly one consumer, a convolution called with `in_act = ACT_LRELU`, whose backward
         multiplies the gradient it hands back by LeakyReLU'(y) (inside its data-gradient kernel where it can) and attaches its
@@ -1002,6 +1004,12 @@ class Conv2d(torch.autograd.Function):
         ctx.noise = noise_eps if noise_w is not None else None
         ctx.res_noise = res_noise_eps if res_noise_w is not None else None
         ctx.res_sink = res_sink
+        ctx.reflect = bool(reflect)
+        if ctx.reflect:
+            assert ((kh, kw, stride, pad, ups) == (3, 3, 1, 1, 0) and not ctx.thin and act == L.ACT_NONE and res is None
+                    and noise_w is None and res_noise_w is None and not stats and not ctx.in_act), "reflect: a plain 3 x 3 layer"
+            L.call("reflect_ring_fwd", x, w, out, n, hi, wi, ci, cin_s, co, cout_s)
+            out.dsee_amax = None      # (a bound its producer measured no longer holds on the border)
         save_with_operand(ctx, vkeep, x, w, out if act != L.ACT_NONE else None)
         return out
 
@@ -1082,6 +1090,17 @@ class Conv2d(torch.autograd.Function):
             dw = _wino_wgrad(x, g, geom.N, geom.Hi, geom.Wi, geom.Cin, geom.Cout, co, ci, vkeep, sums=sums)
         elif ctx.needs_input_grad[1]:
             dw = wgrad_raw(x, g, geom, co, ci, kh, kw, amax_cache=getattr(ctx, "amax_cache", None), exact=ctx.exact)
+        if ctx.reflect:
+            # the border terms of the reflection padding, added in place to what the zero-padded paths above produced
+            if dx is not None:
+                assert dx.is_contiguous()
+                L.call("reflect_ring_dgrad", g, w, dx, geom.N, geom.Hi, geom.Wi, ci, geom.Cin, co, geom.Cout)
+                dx.dsee_amax = None
+            if dw is not None:
+                assert dw.is_contiguous()
+                nbytes = L.lib().dsee_reflect_ring_wgrad_workspace(geom.N, geom.Hi, geom.Wi, ci, co)
+                L.call("reflect_ring_wgrad", x, g, scratch(nbytes, "ringw"), C.c_size_t(nbytes), dw, geom.N, geom.Hi, geom.Wi,
+                       ci, geom.Cin, co, geom.Cout)
         if sums is not None and sums.get("dbias") is not None:
             db = sums["dbias"][:co]
         elif ctx.has_bias and ctx.needs_input_grad[2]:
@@ -1111,7 +1130,7 @@ class Conv2d(torch.autograd.Function):
             tag_amax(gx, amax_slot())
             L.call("act_bwd_amax", dx.contiguous(), x, gx, C.c_long(dx.numel()), ctx.in_act, LRELU_SLOPE, gx.dsee_amax)
             dx = gx
-        return dx, dw, db, dres, None, None, None, None, dnw, None, drnw, None, None, None, None, None, None
+        return dx, dw, db, dres, None, None, None, None, dnw, None, drnw, None, None, None, None, None, None, None
 
 
 class GradSink:
@@ -1189,16 +1208,20 @@ def _thin_ok(x, w, res, stride, pad, ups, noise, res_noise):
 
 
 def conv2d(x, w, bias=None, res=None, stride=1, pad=1, ups=0, act=L.ACT_NONE, noise=None, res_noise=None, res_sink=None,
-           stats=False, in_act=0, defer_act_bwd=False):
+           stats=False, in_act=0, defer_act_bwd=False, reflect=False):
     """`noise` = (noise_w, eps): the NoiseInjection that follows the conv; `res_noise` = (noise_w, eps): the
     NoiseInjection on the residual (the shortcut x_s = noise_skip(x)).  PhiloxNormal draws on a Winograd layer ride in
     the output transform; anything else (a replayed tensor, a non-Winograd layer) runs as its own UpNoise pass.
     `res_sink` (GradSink): the residual's gradient is handed to the norm backward instead of the autograd engine.
     `stats`: the output feeds a training-mode BatchNorm -- a Winograd layer then writes the statistics rows in its output
     transform (bn_stats finds them on the tensor).
-    `in_act` / `defer_act_bwd`: see Conv2d.forward (x is the LeakyReLU output of a layer called with defer_act_bwd)."""
+    `in_act` / `defer_act_bwd`: see Conv2d.forward (x is the LeakyReLU output of a layer called with defer_act_bwd).
+    `reflect`: reflection padding instead of zero padding (Conv2d.forward)."""
     if not (torch.is_grad_enabled() and x.requires_grad):
         in_act = 0
+    if reflect:
+        assert noise is None and res_noise is None and res is None and act == L.ACT_NONE
+        return Conv2d.apply(x, w, bias, None, stride, pad, ups, act, None, None, None, None, None, False, False, 0, False, True)
     if _thin_ok(x, w, res, stride, pad, ups, noise, res_noise):
         co, ci = w.shape[0], w.shape[1]
         kh, kw = w.shape[2], w.shape[3]
@@ -1377,6 +1400,41 @@ class InstNormAct(torch.autograd.Function):
         if ao is not None:
             tag_amax(dx, ao)
         return dx, None
+
+
+class InstNormRes(torch.autograd.Function):
+    """act(res + InstanceNorm(x)): the closing `x + conv_block(x)` of the pix2pixHD ResnetBlock (ablation.py:26-29) in the norm's own
+    pass (dsee_norm_act_res_fwd).  Backward: the IN backward on the saved output; the residual's gradient is g = dy act'(y) itself
+    and goes back through the autograd engine (its fan-in add with the gradient of the block's first convolution: DESIGN 3.17)."""
+
+    @staticmethod
+    def forward(ctx, x, res, act):
+        n, h, w, c = x.shape
+        assert res.shape == x.shape
+        mean, invstd = new(n, c), new(n, c)
+        ws = scratch(L.lib().dsee_norm_workspace(n, h * w, c, n), "norm")
+        L.call("norm_stats", x, n, h * w, c, n, BN_EPS, 0.0, mean, invstd, None, None, ws)
+        y = torch.empty_like(x)
+        L.call("norm_act_res_fwd", x, mean, invstd, res.contiguous(), y, n, h * w, c, n, act, LRELU_SLOPE, None)
+        ctx.act = act
+        ctx.save_for_backward(x, y, mean, invstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, mean, invstd = ctx.saved_tensors
+        n, h, w, c = x.shape
+        dy = dy.contiguous()
+        dx = torch.empty_like(x)
+        ws = scratch(L.lib().dsee_norm_workspace(n, h * w, c, n), "norm")
+        L.call("norm_act_bwd_amax", dy, y, x, mean, invstd, dx, n, h * w, c, n, ctx.act, LRELU_SLOPE, ws, None)
+        dres = None
+        if ctx.needs_input_grad[1]:
+            dres = dy
+            if ctx.act != L.ACT_NONE:
+                dres = torch.empty_like(dy)
+                L.call("act_bwd", dy, y, dres, C.c_long(dy.numel()), ctx.act, LRELU_SLOPE)
+        return dx, dres, None
 
 
 class BatchNormAct(torch.autograd.Function):

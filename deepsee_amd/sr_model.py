@@ -23,20 +23,40 @@ from .optim import FlatAdam
 from .plan import from_opt as plan_from_opt
 
 
+NETG_VALUES = ("deepsee", "nostyle", "nospadenostyle", "puresean")
+
+
 def block_plan(opt):
     """sr.py:27-51: head_0 SPADE ('late' in norm_G), SEAN blocks, PureSEAN tail iff
     load_size >= 512.  Every layer's param-free norm follows norm_G (networks.param_free_norm_of: raises for a norm_G this build
-    does not run)."""
+    does not run).
+
+    opt.netG (NETG_VALUES; an opt without the field: 'deepsee') selects one of the generators of ablation.py instead, by the names
+    its find_network_using_name(netG, 'ablation') resolves; any other value raises ValueError:
+      nostyle         every block SPADE (style=False), the tail beyond the fourth block PureSEAN iff load_size >= 512
+                      (ablation.py:57-74: puresean=True wins over style=False)
+      puresean        every block PureSEAN, head included (ablation.py:244-261)
+      nospadenostyle  every block the pix2pixHD ResnetBlock, kind 'resnet' (ablation.py:13-29, 151-168)"""
     N.param_free_norm_of(opt.norm_G)
+    netG = getattr(opt, "netG", "deepsee")
+    if not isinstance(netG, str) or netG not in NETG_VALUES:
+        raise ValueError("netG %r: expected one of %s" % (netG, ", ".join(NETG_VALUES)))
     nb = int(round(math.log2(opt.crop_size) - math.log2(opt.start_size)))
     cfg = opt.norm_G.replace("spectral", "")
     sk = "sean" if "sean" in cfg else "spade"
     early = "late" not in opt.norm_G
-    plan = [("head_0", sk if early else "spade"), ("G_middle_0", sk), ("G_middle_1", sk)]
+    head, tail = (sk if early else "spade"), "puresean"
+    if netG == "nostyle":
+        head = sk = "spade"
+    elif netG == "puresean":
+        head = sk = "puresean"
+    elif netG == "nospadenostyle":
+        head = sk = tail = "resnet"
+    plan = [("head_0", head), ("G_middle_0", sk), ("G_middle_1", sk)]
     max_nb = 4 if opt.load_size >= 512 else 99
     kinds = [sk] * max(0, min(nb, max_nb) - 1)
     if max_nb != 99:
-        kinds += ["puresean"] * max(0, nb - max_nb)
+        kinds += [tail] * max(0, nb - max_nb)
     return plan + [("up_list.%d" % i, k) for i, k in enumerate(kinds)]
 
 

@@ -973,6 +973,31 @@ int dsee_spade_resblock_bwd(const dsee_norm_layer* norm_0, const float* w_conv_0
                             const dsee_block_grads* grads, float* dx, float* amax_dx, float slope, int N, int H, int W, int C,
                             const void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* ---- reflection padding of a 3x3 / stride 1 convolution as a border pass (csrc/reflect_ring.hip): the pix2pixHD
+ * ResnetBlock of the netG ablation `nospadenostyle` (`ablation.py:13-29`: nn.ReflectionPad2d(1) + Conv2d(k=3)).
+ *     conv3x3(reflect_pad(x), w) = conv3x3(zero_pad(x), w) + ring(x, w)
+ * ring is non-zero on output row 0, row H-1, column 0, column W-1: at a border output the sum over the taps whose padded
+ * coordinate lies outside the map of w[co][ci][kh][kw] * x[r(i)][r(j)][ci], r(-1) = 1, r(H) = H-2 (3 taps on an edge, 5 in a
+ * corner).  The zero-padded layer runs on dsee_conv2d_fwd / the Winograd path; these add the border terms IN PLACE (one writer per
+ * element, no atomics), exact fp32 on v_mfma_f32_16x16x4_f32.  x / dx: [N][H][W][Cin_stored], y / dy: [N][H][W][Cout_stored],
+ * w / dw: OIHW [Cout][Cin][3][3]; *_stored = the count padded to a multiple of 4.  H < 2, W < 2, a NULL pointer or a stored
+ * count that is not the padded count: DSEE_EINVAL, nothing launched.
+ *   fwd:   y[border] += ring(x, w)
+ *   dgrad: dx rows 1, H-2 and columns 1, W-2 += sum_co w * dy[border] (gather form)
+ *   wgrad: dw[co][ci][kh][kw] += sum over the border pixels whose tap (kh, kw) is outside of dy[p][co] * x[r(p)][ci]; K is split
+ *          over blocks whose partial tiles (workspace) are folded in split order -- a function of the shape alone */
+int dsee_reflect_ring_fwd(const float* x, const float* w_oihw, float* y, int N, int H, int W, int Cin, int Cin_stored, int Cout,
+                          int Cout_stored, hipStream_t stream);
+int dsee_reflect_ring_dgrad(const float* dy, const float* w_oihw, float* dx, int N, int H, int W, int Cin, int Cin_stored, int Cout,
+                            int Cout_stored, hipStream_t stream);
+size_t dsee_reflect_ring_wgrad_workspace(int N, int H, int W, int Cin, int Cout);
+int dsee_reflect_ring_wgrad(const float* x, const float* dy, float* workspace, size_t workspace_bytes, float* dw_oihw, int N, int H,
+                            int W, int Cin, int Cin_stored, int Cout, int Cout_stored, hipStream_t stream);
+/* y = act((x - mean) * invstd + res): dsee_norm_act_fwd_amax with a residual operand -- the closing `x + InstanceNorm(conv(.))` of
+ * that block (`ablation.py:26-29`).  Its backward is dsee_norm_act_bwd_amax on the saved y (dres = dy * act'(y)). */
+int dsee_norm_act_res_fwd(const float* x, const float* mean, const float* invstd, const float* res, float* y, int N, int HW, int C,
+                          int groups, int act, float slope, float* amax_y, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
