@@ -368,6 +368,12 @@ class SRModel(nn.Module):
             if net is not None and label in states:
                 self.load_net_state(net, states[label])
 
+    def native_generator(self):
+        """The generator of this model's current netSR weights behind the C entry points alone (deepsee_amd.native.NativeGenerator:
+        mode "demo" as dsee_generator_prepare + dsee_generator_fwd).  A snapshot: later training steps do not reach it."""
+        from .native import NativeGenerator
+        return NativeGenerator(self.opt, self.netSR.state_dict())
+
     # ---- data plumbing
     def _native(self, data):
         """Accepts the manager's native dict (NHWC tensors + ops.Labels) or the reference's dict (one-hot NCHW

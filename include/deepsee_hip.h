@@ -793,6 +793,14 @@ int dsee_sean_pack_bwd(const float* w_gamma, const float* w_beta, const float* w
 /* per-image style tables (normalization.py:182-185 as a table, SURVEY B-7): [N*L][9*rows] GEMM result <-> [N][9][rows][32] */
 int dsee_style_table_layout(const float* t, float* table, int N, int L, int rows, float* amax, hipStream_t stream);
 int dsee_style_table_layout_bwd(const float* dtable, float* dt, int N, int L, int rows, hipStream_t stream);
+/* The same tables without a library GEMM (deepsee_amd/csrc/style_table.hip): the product and the layout in one kernel,
+ *   table[n][tap][row][r] = sum_s wst[tap*rows + row][s] * style[n][r][s]  (r < L),  0  (L <= r < 32)
+ * style [N][L][S], wst [9*rows][S] as dsee_sean_pack_fwd writes it, table [N][9][rows][32].  Exact fp32 on
+ * v_mfma_f32_16x16x4_f32, one writer per element, a summation order that depends on S alone: bit-reproducible.  amax (optional)
+ * is the slot of dsee_style_table_layout: it receives max |table| ON TOP of what it holds (max |w2a| from dsee_sean_pack_fwd), in
+ * the 64-line form of dsee_absmax.  1 <= L <= 32, S % 4 == 0, rows % 64 == 0 (DSEE_EUNSUPPORTED otherwise, nothing launched). */
+int dsee_style_table_fwd(const float* style, const float* wst, float* table, int N, int L, int S, int rows, float* amax,
+                         hipStream_t stream);
 
 /* ------------------------------------------------------------------ spectral norm + Adam */
 int dsee_spectral_norm_fwd(const float* w_orig, float* u, float* v, float* sigma, float* w_sn, int R, int K,
@@ -997,6 +1005,91 @@ int dsee_reflect_ring_wgrad(const float* x, const float* dy, float* workspace, s
  * that block (`ablation.py:26-29`).  Its backward is dsee_norm_act_bwd_amax on the saved y (dres = dy * act'(y)). */
 int dsee_norm_act_res_fwd(const float* x, const float* mean, const float* invstd, const float* res, float* y, int N, int HW, int C,
                           int groups, int act, float slope, float* amax_y, hipStream_t stream);
+
+/* ---- the whole generator forward from C (deepsee_amd/csrc/coarse.cpp): SRModel mode "demo" (`sr_model.py:100-108`, `sr.py:54-98`)
+ * for the `deepsee` generator in fp32 with BatchNorm running statistics -- LR image + label map + style matrix -> HR image,
+ * bit-identical to the Python module under the default kernel plan (tests/test_gpu_capi_generator.py).
+ *
+ * The checkpoint is ONE flat fp32 device buffer; dsee_generator_desc, a HOST struct without device pointers, names the network and
+ * the offset (in floats, -1 = absent) of every tensor in it under the reference's state-dict keys (deepsee_amd/native.py::layout
+ * writes both).  Blocks in forward order: head_0, G_middle_0, G_middle_1, up_list.*; `ups` = the block's input is nearest-upsampled
+ * x2 first (`sr.py:57`).  levels = the number of blocks with ups; H = h << levels, W = w << levels.
+ *
+ *   dsee_generator_prepare  everything that depends on the weights only, once per checkpoint, into the caller-owned `prepared`
+ *       buffer: eval-mode spectral norm of all convolutions (sigma from the stored u, v: dsee_spectral_norm_group_fwd with
+ *       power_iter = 0) and their Winograd-domain fp16x2 weights with maxima, per norm layer dsee_sean_pack_fwd (w2a, wst, packed
+ *       bias, max |w2a|), the mlp_shared gather table, the Winograd-domain (SPADE) or packed direct-kernel (SEAN) gamma|beta
+ *       weights, the packed weights of `initial` and `conv_img`.  Copies three small tables from the host and synchronises the
+ *       stream before it returns: not capturable.
+ *   dsee_generator_fwd      everything else on `stream`: NCHW -> NHWC, `initial`, per block the nearest upsample, per SEAN norm
+ *       dsee_style_table_fwd from `style`, the norm / Winograd sequence of dsee_spade_resblock_fwd (per level the kernels the Python
+ *       path picks: the fused norm kernel, or the direct one where a SEAN level has (h/4)(w/4) % 128 != 0; the pre-split GEMM from
+ *       512 tiles of 256 x 256 on, the fp32-operand one below), LeakyReLU in the last block's epilogue, conv_img + tanh,
+ *       NHWC -> NCHW.  No allocation, no synchronisation, no host -> device copy: capturable into a hipGraph.  Reads `params` and
+ *       `prepared`, writes `out` and `workspace` only.
+ *
+ * image_lr [N][3][h][w] NCHW in [-1, 1]; labels uint8 [N][lab_h][lab_w] at the HR resolution; style [N][label_nc][S];
+ * out [N][3][H][W] NCHW.  The two size functions take scalars only and return an upper bound that does not depend on the block
+ * kinds (every norm sized as SEAN); the entry points check against the same numbers.
+ *
+ * Checked before the first launch, from the scalars and the host struct alone, in this order: NULL arguments (DSEE_EINVAL); kinds
+ * and shape rules (DSEE_EUNSUPPORTED, the message names the level and the rule); the label map against H x W (DSEE_EINVAL); buffer
+ * sizes (DSEE_EINVAL, the message names the bytes needed and the size function).  Supported: kinds SPADE and SEAN, norm ==
+ * DSEE_GEN_NORM_BATCH, precision == DSEE_GEN_FP32, 1 <= n_blocks <= DSEE_GEN_MAX_BLOCKS, label_nc in 1..32, S % 4 == 0, and at
+ * every level C % 128 == 0, H, W % 4 == 0, (H/4)(W/4) % 64 == 0, N (H/4)(W/4) % 256 == 0, no SEAN level above max_fm_size on
+ * either axis.  Not built (DSEE_EUNSUPPORTED): PureSEAN blocks (the tail of load_size >= 512; netG = puresean), ResnetBlocks
+ * (netG = nospadenostyle), the capped path above max_fm_size, the dense path below 32 x 32, InstanceNorm norm_G, the 16-bit mode. */
+#define DSEE_GEN_MAX_BLOCKS 12
+#define DSEE_GEN_SPADE 0
+#define DSEE_GEN_SEAN 1
+#define DSEE_GEN_PURESEAN 2
+#define DSEE_GEN_RESNET 3
+#define DSEE_GEN_NORM_BATCH 0
+#define DSEE_GEN_NORM_INSTANCE 1
+#define DSEE_GEN_FP32 0
+#define DSEE_GEN_FP16 1
+typedef struct dsee_generator_conv {   /* spectral_norm(nn.Conv2d(C, C, 3)): `architecture.py:40-44` */
+  int64_t weight_orig;  /* [C][C][3][3] */
+  int64_t bias;         /* [C] */
+  int64_t weight_u;     /* [C] */
+  int64_t weight_v;     /* [9 C] */
+} dsee_generator_conv;
+typedef struct dsee_generator_norm {   /* SPADE / SEAN_Block: `normalization.py:71-213` */
+  int64_t w_shared, b_shared;           /* mlp_shared.0: [128][label_nc][3][3], [128] */
+  int64_t w_gamma, b_gamma;             /* mlp_gamma: [C][128][3][3], [C] */
+  int64_t w_beta, b_beta;
+  int64_t ws_gamma, bs_gamma;           /* mlp_style_gamma: [C][S][3][3], [C] (SEAN; -1 otherwise) */
+  int64_t ws_beta, bs_beta;
+  int64_t alpha_gamma, alpha_beta;      /* [1] each, before the sigmoid (SEAN) */
+  int64_t running_mean, running_var;    /* param_free_norm: [C] */
+} dsee_generator_norm;
+typedef struct dsee_generator_block {
+  int32_t kind;          /* DSEE_GEN_* */
+  int32_t ups;           /* 1: nearest x2 in front of the block */
+  dsee_generator_conv conv_0, conv_1;
+  dsee_generator_norm norm_0, norm_1;
+} dsee_generator_block;
+typedef struct dsee_generator_desc {
+  int32_t C;             /* 16 ngf */
+  int32_t label_nc;      /* classes of the label map (semantic_nc) */
+  int32_t S;             /* regional_style_size */
+  int32_t max_fm_size;
+  int32_t n_blocks;
+  int32_t norm;          /* DSEE_GEN_NORM_* : the param-free norm of norm_G */
+  int32_t precision;     /* DSEE_GEN_FP32 | DSEE_GEN_FP16 */
+  int32_t reserved_;
+  int64_t param_floats;  /* length of the flat parameter buffer */
+  int64_t initial_w, initial_b;     /* [C][3][3][3], [C] */
+  int64_t conv_img_w, conv_img_b;   /* [3][C][3][3], [3] */
+  dsee_generator_block blocks[DSEE_GEN_MAX_BLOCKS];
+} dsee_generator_desc;
+size_t dsee_generator_prepared_bytes(int C, int label_nc, int S, int n_blocks);
+size_t dsee_generator_fwd_workspace(int C, int label_nc, int levels, int N, int h, int w);
+int dsee_generator_prepare(const dsee_generator_desc* desc, const float* params, void* prepared, size_t prepared_bytes,
+                           hipStream_t stream);
+int dsee_generator_fwd(const dsee_generator_desc* desc, const float* params, const void* prepared, size_t prepared_bytes,
+                       const float* image_lr, const uint8_t* labels, int lab_h, int lab_w, const float* style, float* out, int N,
+                       int h, int w, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 #ifdef __cplusplus
 }
