@@ -9,6 +9,7 @@ import os
 import ctypes as C
 
 import threading
+from collections import namedtuple
 from typing import NamedTuple, Optional
 
 import torch
@@ -388,30 +389,19 @@ def _frozen_cache(w, key, build):
     return cache[key]
 
 
-def _pack_fwd(w, cin_s, korder):
+def _pack(kind, w, c_s, korder):
+    """Packed weights of a direct kernel with the maximum w carries.  "fwd": one row per output channel, c_s = padded Cin;
+    "dgrad": one row per input channel, c_s = padded Cout."""
     def build():
         co, ci, kh, kw = w.shape
-        wp = new(L.wrows(L.pad4(co)), L.kpad(kh, kw, cin_s))
-        L.call("pack_weight_fwd", w, None, None, wp, co, ci, kh, kw, cin_s, korder)
+        wp = new(L.wrows(L.pad4(co if kind == "fwd" else ci)), L.kpad(kh, kw, c_s))
+        L.call("pack_weight_" + kind, w, None, None, wp, co, ci, kh, kw, c_s, korder)
         wp.dsee_amax = getattr(w, "dsee_amax", None)     # (a permutation + zero padding of w: same maximum)
         if wp.dsee_amax is None and getattr(w, "dsee_frozen", False):
             wp.dsee_amax = torch.zeros(AMAX_FLOATS, dtype=torch.float32, device=wp.device)
             L.call("absmax", wp, wp.numel(), wp.dsee_amax)
         return wp
-    return _frozen_cache(w, ("fwd", cin_s, korder), build)
-
-
-def _pack_dgrad(w, cout_s, korder):
-    def build():
-        co, ci, kh, kw = w.shape
-        wp = new(L.wrows(L.pad4(ci)), L.kpad(kh, kw, cout_s))
-        L.call("pack_weight_dgrad", w, None, None, wp, co, ci, kh, kw, cout_s, korder)
-        wp.dsee_amax = getattr(w, "dsee_amax", None)
-        if wp.dsee_amax is None and getattr(w, "dsee_frozen", False):
-            wp.dsee_amax = torch.zeros(AMAX_FLOATS, dtype=torch.float32, device=wp.device)
-            L.call("absmax", wp, wp.numel(), wp.dsee_amax)
-        return wp
-    return _frozen_cache(w, ("dgrad", cout_s, korder), build)
+    return _frozen_cache(w, (kind, c_s, korder), build)
 
 
 def tensor_amax(t, cache=None):
@@ -450,7 +440,7 @@ def _dgrad_stride2_parity(g, w, geom, ci, amax_cache=None, exact=False):
         w4.dsee_amax = w.dsee_amax                    # (a permutation of w: same maximum)
     korder = 1 if geom.Cout % 32 == 0 else 0
     gd = L.ConvGeom(n, geom.Ho, geom.Wo, geom.Cout, ha, wa, 4 * cin_s, 2, 2, 1, 1, -1, 0, 0, korder)
-    z = conv_raw(g, _pack_dgrad(w4, geom.Cout, korder), gd, amax_cache=amax_cache, exact=exact)
+    z = conv_raw(g, _pack("dgrad", w4, geom.Cout, korder), gd, amax_cache=amax_cache, exact=exact)
     dx = z.view(n, ha, wa, 2, 2, cin_s).permute(0, 1, 3, 2, 4, 5).reshape(n, 2 * ha, 2 * wa, cin_s)
     dx = dx[:, :h, :wd].contiguous() if (2 * ha != h or 2 * wa != wd) else dx.contiguous()
     if carried_amax(z) is not None:
@@ -948,66 +938,184 @@ def _wino_wgrad(x, g, n, h, wd, cin_s, cout_s, co, ci, v_fwd=None, w_for_dx=None
     return (total, dx) if with_dx else total
 
 
+# ---- the convolution node: its kernel families are chosen once per layer (_conv_path); its backward is the steps below, in order
+THIN3, WINO, DIRECT = "thin3", "wino", "direct"     # forward / weight gradient: thin.hip's 3 x 3 kernels | Winograd | implicit GEMM
+THIN1, ADJOINT = "thin1", "adjoint"    # both gradients by one dsee_thin1x1_bwd (conv2d's thin path) | dx from the Winograd wgrad dM
+S2_PARITY, DIRECT_SUMPOOL = "s2_parity", "direct_sumpool"     # data gradient: _dgrad_stride2_parity | direct + sumpool (ups)
+# dgrad / wgrad: None where the gradient is not needed; keep_v: the forward keeps V of x for the weight gradient; g_amax: the
+# activation backward attaches max |g|; dout_sums: bias / noise-weight gradients can ride in the weight gradient's A dY A^T pass
+ConvPath = namedtuple("ConvPath", "fwd dgrad wgrad keep_v g_amax dout_sums")
+# all of a Conv2d call that autograd does not differentiate (Conv2d.forward, conv2d); *_eps: the draws behind the noise weights
+ConvSpec = namedtuple("ConvSpec", "stride pad ups act noise_eps res_noise_eps res_sink exact stats in_act defer_act_bwd reflect",
+                      defaults=(1, 1, 0, L.ACT_NONE, None, None, None, False, False, 0, False, False))
+
+
+def _conv_path(n, hi, wi, cin_s, cout_s, co, ci, kh, kw, stride, pad, ups, has_res, exact, need_dx, need_dw):
+    """The ConvPath of a layer of this geometry under the active plan: no tensors, no launches.  What depends on run-time tensor
+    state (a carried maximum, a chunked batch, pre_dm / pk) is decided by the helpers that own it."""
+    geom = L.geom_fwd(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
+    wino = _wino_ok(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
+    thin3 = (not P().thin_gemm and kh == 3 and stride == 1 and pad == 1 and ups == 0 and co <= 4 and cin_s % 256 == 0
+             and cin_s <= 1024 and wi % 64 == 0 and not has_res)
+    thin1 = (P().thin_gemm and kh == 1 and kw == 1 and ups == 0 and co <= 32 and ci == cin_s and not has_res
+             and geom.Ho == hi and geom.Wo == wi and cin_s >= 128)
+    mode = _wgrad_mode(cin_s, cout_s)
+    wino_w = wino and P().winograd_wgrad and need_dw
+    adjoint = wino_w and mode != 1 and _adjoint_ok(cout_s, cin_s)      # one A dY A^T of g serves both gradients
+    dgrad = (None if not need_dx else THIN1 if thin1 else ADJOINT if adjoint else WINO if wino
+             else S2_PARITY if _s2_parity_ok(geom, kh, kw) else DIRECT_SUMPOOL if ups else DIRECT)
+    wgrad = None if not need_dw else THIN1 if thin1 else THIN3 if thin3 else WINO if wino_w else DIRECT
+    keep_v = wino and not thin3 and P().keep_v and need_dw and mode == 2
+    g_amax = P().presplit_dm if wino else (_direct_split_on(exact) and P().conv_amax_out)
+    dout_sums = wino_w and _dout_sums_ok(n, _wino_chunk(n, hi, wi, max(cin_s, cout_s)), cout_s, mode)
+    return ConvPath(THIN3 if thin3 else WINO if wino else DIRECT, dgrad, wgrad, bool(keep_v), bool(g_amax), bool(dout_sums))
+
+
+def _act_bwd(dy, out, act, with_amax, deferred=False):
+    """g = dy act'(out); `deferred`: the consumer's backward already applied act'(out) and tagged max |g| (Conv2d.forward).
+    `with_amax`: max |g| is attached, the bound the kernels that read g scale or split it with."""
+    if deferred or act == L.ACT_NONE:
+        return dy
+    g = torch.empty_like(dy)
+    amax = (tag_amax(g, amax_slot()),) if with_amax else ()
+    L.call("act_bwd_amax" if with_amax else "act_bwd", dy, out, g, C.c_long(dy.numel()), act, LRELU_SLOPE, *amax)
+    return g
+
+
+def _thin1_grads(x, w, g, geom, need_dx, need_dw, in_act):
+    """(dx, dw) of the 1 x 1 layer with <= 32 outputs.  `in_act`: the producer of x = LeakyReLU(.) deferred its activation's
+    backward to this kernel, which then also writes max |dx|."""
+    co, ci = w.shape[0], w.shape[1]
+    dx, dw = (torch.empty_like(x) if need_dx else None), (new(co, ci, 1, 1) if need_dw else None)
+    ws = scratch(L.lib().dsee_thin1x1_bwd_workspace(geom.Cin, co), "wgrad") if need_dw else None
+    da = tag_amax(dx, amax_slot()) if (need_dx and in_act) else None
+    L.call("thin1x1_bwd", g, geom.Cout, w, x, dx, dw, C.c_long(geom.N * geom.Hi * geom.Wi), geom.Cin, co, ws, int(da is not None),
+           LRELU_SLOPE, da)
+    return dx, dw
+
+
+def _conv_dgrad(family, x, w, g, geom, direct):
+    """dx by the rotated-kernel Winograd convolution | by output parity | by the direct kernel (+ sumpool under an upsampling)"""
+    if family == WINO:
+        return _wino_conv(g, w, geom.N, geom.Ho, geom.Wo, geom.Cin, geom.Cout, True)
+    if family == S2_PARITY:
+        return _dgrad_stride2_parity(g, w, geom, w.shape[1], **direct)
+    gd = L.geom_dgrad(geom)
+    dx = conv_raw(g, _pack("dgrad", w, geom.Cout, gd.korder), gd, **direct)
+    if family == DIRECT_SUMPOOL:
+        dxl, dx = dx, torch.empty_like(x)
+        L.call("sumpool", dxl, dx, geom.N, gd.Ho, gd.Wo, geom.Cin, geom.ups)
+    return dx
+
+
+def _conv_wgrad(family, x, w, g, geom, vkeep, sums, direct):
+    co, ci, kh, kw = w.shape
+    if family == WINO:
+        return _wino_wgrad(x, g, geom.N, geom.Hi, geom.Wi, geom.Cin, geom.Cout, co, ci, vkeep, sums=sums)
+    if family == DIRECT:
+        return wgrad_raw(x, g, geom, co, ci, kh, kw, **direct)
+    ws = scratch(L.lib().dsee_conv3x3_thin_wgrad_workspace(geom.Cin), "wgrad")       # THIN3
+    dw = new(co, ci, 3, 3)
+    L.call("conv3x3_thin_wgrad", x, g, ws, dw, geom.N, geom.Hi, geom.Wi, geom.Cin, co, ci)
+    return dw
+
+
+def _conv_grads(path, x, w, g, geom, vkeep, sums, in_act, direct):
+    """(dx, dw) by the families of `path`, the data gradient first; `direct`: amax_cache / exact of the direct kernels"""
+    if THIN1 in (path.dgrad, path.wgrad):
+        return _thin1_grads(x, w, g, geom, path.dgrad == THIN1, path.wgrad == THIN1, in_act)
+    if path.dgrad == ADJOINT:
+        return _wino_wgrad(x, g, geom.N, geom.Hi, geom.Wi, geom.Cin, geom.Cout, *w.shape[:2], vkeep, w_for_dx=w, sums=sums)[::-1]
+    dx = _conv_dgrad(path.dgrad, x, w, g, geom, direct) if path.dgrad else None
+    dw = _conv_wgrad(path.wgrad, x, w, g, geom, vkeep, sums, direct) if path.wgrad else None
+    return dx, dw
+
+
+def _reflect_border_grads(x, w, g, dx, dw, geom):
+    """The border terms of the reflection padding, added in place to what the zero-padded paths produced."""
+    dims = (geom.N, geom.Hi, geom.Wi, w.shape[1], geom.Cin, w.shape[0], geom.Cout)
+    if dx is not None:
+        L.call("reflect_ring_dgrad", g, w, dx, *dims)
+        dx.dsee_amax = None
+    if dw is not None:
+        nbytes = L.lib().dsee_reflect_ring_wgrad_workspace(geom.N, geom.Hi, geom.Wi, w.shape[1], w.shape[0])
+        L.call("reflect_ring_wgrad", x, g, scratch(nbytes, "ringw"), C.c_size_t(nbytes), dw, *dims)
+
+
+def _noise_wgrad(g, eps):
+    """gradient [C] of a NoiseInjection weight: sum over pixels of g x the regenerated draw `eps` (a PhiloxNormal)"""
+    cn = g.shape[-1]
+    m, d = g.numel() // cn, new(cn)
+    L.call("channel_dot_rng", g, d, m, cn, scratch(L.lib().dsee_channel_dot_workspace(m, cn), "chdot"), eps.seed, eps.offset)
+    return d
+
+
+def _conv_side_grads(g, co, want, sums, res_sink):
+    """(db, dres, dnw, drnw) of the entries of `want` (_wino_dout's, + "res").  Bias and noise weights: what the A dY A^T pass left
+    in `sums`, else channel_dot / channel_dot_rng passes over g; the residual's is g itself, returned or put into the GradSink."""
+    if want["res"] and res_sink is not None:
+        res_sink.put(g)      # picked up as the `add` operand of the norm backward that also feeds on `res`
+    dres = g if (want["res"] and res_sink is None) else None
+    if sums is not None:
+        return (sums["dbias"][:co] if want["bias"] else None), dres, sums["dn0"], sums["dn1"]
+    db = channel_dot(g, None, co).clone() if want["bias"] else None
+    return db, dres, *(None if eps is None else _noise_wgrad(g, eps) for eps in (want["n0"], want["n1"]))
+
+
+IN_X, IN_W, IN_BIAS, IN_RES, IN_NOISE_W, IN_RES_NOISE_W, IN_SPEC = range(7)     # Conv2d.apply's inputs in needs_input_grad
+
+
 class Conv2d(torch.autograd.Function):
     """out = act(conv(x, w) + bias + residual); x stored [N,H,W,pad4(Cin)], w OIHW (real channel counts)."""
 
     @staticmethod
-    def forward(ctx, x, w, bias, res, stride, pad, ups, act, noise_w=None, noise_eps=None, res_noise_w=None,
-                res_noise_eps=None, res_sink=None, exact=False, stats=False, in_act=0, defer_act_bwd=False, reflect=False):
-        """`reflect`: the padding is nn.ReflectionPad2d(1) instead of zeros (3 x 3, stride 1, no epilogue but the bias): the
-        zero-padded layer runs as always and dsee_reflect_ring_* add the border terms in place, here and in backward.
-        `exact`: keep a direct convolution on the fp32 MFMA (no operand-maximum passes over its activations).
+    def forward(ctx, x, w, bias, res, noise_w, res_noise_w, spec):
+        """The fields of `spec` (ConvSpec) -- `reflect`: the padding is nn.ReflectionPad2d(1) instead of zeros (3 x 3, stride 1, no
+        epilogue but the bias): the zero-padded layer runs as always and dsee_reflect_ring_* add the border terms in place, here and
+        in backward.  `exact`: keep a direct convolution on the fp32 MFMA (no operand-maximum passes over its input).
         `defer_act_bwd` / `in_act` are the two halves of ONE contract set up by the caller (networks.DeepSEESR.forward): this
         layer's output y = LeakyReLU(.) has exactly one consumer, a convolution called with `in_act = ACT_LRELU`, whose backward
         multiplies the gradient it hands back by LeakyReLU'(y) (inside its data-gradient kernel where it can) and attaches its
         maximum; this layer's backward then skips its own pass over (dy, y) -> g."""
-        ctx.plan = P()
-        ctx.exact = bool(exact)
-        ctx.in_act, ctx.defer_act_bwd = int(in_act or 0), bool(defer_act_bwd)
-        assert ctx.in_act in (0, L.ACT_LRELU) and (not ctx.defer_act_bwd or act == L.ACT_LRELU)
-        _bind_rng(noise_eps, res_noise_eps)
-        co, ci, kh, kw = w.shape
-        n, hi, wi, cin_s = x.shape
+        ctx.plan, ctx.spec = P(), spec
+        stride, pad, ups, act = spec[:4]
+        assert spec.in_act in (0, L.ACT_LRELU) and (not spec.defer_act_bwd or act == L.ACT_LRELU)
+        _bind_rng(spec.noise_eps, spec.res_noise_eps)
+        (n, hi, wi, cin_s), (co, ci, kh, kw) = x.shape, w.shape
         assert cin_s == L.pad4(ci), (cin_s, ci)
         cout_s = L.pad4(co)
         geom = L.geom_fwd(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
-        w_amax, w_u = getattr(w, "dsee_amax", None), getattr(w, "dsee_u", None)   # carried by a spectral-norm group launch
+        path = _conv_path(n, hi, wi, cin_s, cout_s, co, ci, kh, kw, stride, pad, ups, res is not None, spec.exact,
+                          ctx.needs_input_grad[IN_X], ctx.needs_input_grad[IN_W])
+        ctx.w_amax, ctx.w_u = getattr(w, "dsee_amax", None), getattr(w, "dsee_u", None)   # carried by a spectral-norm group launch
         w = w.contiguous()
-        w.dsee_amax = ctx.w_amax = w_amax
-        w.dsee_u = ctx.w_u = w_u
-        vkeep = None
-        ctx.wino = _wino_ok(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
-        ctx.thin = (not P().thin_gemm and kh == 3 and stride == 1 and pad == 1 and ups == 0 and co <= 4 and cin_s % 256 == 0
-                    and cin_s <= 1024 and wi % 64 == 0 and res is None)
-        if ctx.thin:
+        w.dsee_amax, w.dsee_u = ctx.w_amax, ctx.w_u
+        vkeep, ctx.amax_cache = None, None
+        if path.fwd == THIN3:
             out = new(n, hi, wi, cout_s)
             L.call("conv3x3_thin_fwd", x, w, bias, out, n, hi, wi, cin_s, co, act, LRELU_SLOPE)
-        elif ctx.wino:
-            # the fp32 V of x is the weight gradient's Q operand: keep it instead of transforming x again (2.25x the
-            # bytes of x; keep_v = False trades the memory back for one more transform pass)
-            keep = [] if (P().keep_v and ctx.needs_input_grad[1] and _wgrad_mode(cin_s, cout_s) == 2) else None
+        elif path.fwd == WINO:
+            keep = [] if path.keep_v else None
             # bench.py: the whole layer (input transform + GEMMs + output transform) on its algorithmic bytes (x in, y out)
             # and its Winograd-domain FLOPs (2.25 multiplies per output and channel pair instead of 9)
             with _timed("conv_forward@%dx%d %d->%d" % (hi, wi, cin_s, cout_s), 2.0 * 36 * (n * hi * wi // 16) * cin_s * cout_s,
                         4.0 * n * hi * wi * (cin_s + cout_s)):
                 out = _wino_conv(x, w, n, hi, wi, cin_s, cout_s, False, pad_vec(bias, cout_s), res, act, keep=keep,
-                                 noise=None if noise_w is None else (noise_w, noise_eps),
-                                 res_noise=None if res_noise_w is None else (res_noise_w, res_noise_eps), stats=stats)
+                                 noise=None if noise_w is None else (noise_w, spec.noise_eps),
+                                 res_noise=None if res_noise_w is None else (res_noise_w, spec.res_noise_eps), stats=spec.stats)
             vkeep = keep[0] if keep else None
         else:
             ctx.amax_cache = {}   # max |x| found here is reused by the weight gradient
-            out = conv_raw(x, _pack_fwd(w, cin_s, geom.korder), geom, pad_vec(bias, cout_s), res, act,
-                           amax_cache=ctx.amax_cache, exact=ctx.exact)
-        assert noise_w is None or (ctx.wino and act == L.ACT_NONE and isinstance(noise_eps, PhiloxNormal))
-        assert res_noise_w is None or (ctx.wino and res is not None and isinstance(res_noise_eps, PhiloxNormal))
-        ctx.geom, ctx.act, ctx.has_bias, ctx.has_res = geom, act, bias is not None, res is not None
-        ctx.noise = noise_eps if noise_w is not None else None
-        ctx.res_noise = res_noise_eps if res_noise_w is not None else None
-        ctx.res_sink = res_sink
-        ctx.reflect = bool(reflect)
-        if ctx.reflect:
-            assert ((kh, kw, stride, pad, ups) == (3, 3, 1, 1, 0) and not ctx.thin and act == L.ACT_NONE and res is None
-                    and noise_w is None and res_noise_w is None and not stats and not ctx.in_act), "reflect: a plain 3 x 3 layer"
+            out = conv_raw(x, _pack("fwd", w, cin_s, geom.korder), geom, pad_vec(bias, cout_s), res, act,
+                           amax_cache=ctx.amax_cache, exact=spec.exact)
+        assert noise_w is None or (path.fwd == WINO and act == L.ACT_NONE and isinstance(spec.noise_eps, PhiloxNormal))
+        assert res_noise_w is None or (path.fwd == WINO and res is not None and isinstance(spec.res_noise_eps, PhiloxNormal))
+        ctx.geom, ctx.path, ctx.has_bias, ctx.has_res = geom, path, bias is not None, res is not None
+        ctx.noise = spec.noise_eps if noise_w is not None else None
+        ctx.res_noise = spec.res_noise_eps if res_noise_w is not None else None
+        if spec.reflect:
+            assert ((kh, kw, stride, pad, ups) == (3, 3, 1, 1, 0) and path.fwd != THIN3 and act == L.ACT_NONE and res is None
+                    and noise_w is None and res_noise_w is None and not spec.stats and not spec.in_act), "reflect: plain 3 x 3"
             L.call("reflect_ring_fwd", x, w, out, n, hi, wi, ci, cin_s, co, cout_s)
             out.dsee_amax = None      # (a bound its producer measured no longer holds on the border)
         save_with_operand(ctx, vkeep, x, w, out if act != L.ACT_NONE else None)
@@ -1019,118 +1127,18 @@ class Conv2d(torch.autograd.Function):
         (x, w, out), vkeep = saved_with_operand(ctx)
         w.dsee_amax, w.dsee_u = ctx.w_amax, ctx.w_u
         _bind_rng(ctx.noise, ctx.res_noise)
-        geom = ctx.geom
-        co, ci, kh, kw = w.shape
-        dy = dy.contiguous()
-        if ctx.defer_act_bwd:
-            g = dy          # (the consumer's backward already applied LeakyReLU'(out) and tagged max |g|: see forward)
-        elif ctx.act != L.ACT_NONE and ctx.wino and P().presplit_dm:
-            g = torch.empty_like(dy)
-            tag_amax(g, amax_slot())      # (the A dY A^T transform below is written pre-split with this bound)
-            L.call("act_bwd_amax", dy, out, g, C.c_long(dy.numel()), ctx.act, LRELU_SLOPE, g.dsee_amax)
-        elif ctx.act != L.ACT_NONE and not ctx.wino and _direct_split_on(ctx.exact) and P().conv_amax_out:
-            g = torch.empty_like(dy)
-            tag_amax(g, amax_slot())      # (the direct data / weight gradient kernels split g with this bound)
-            L.call("act_bwd_amax", dy, out, g, C.c_long(dy.numel()), ctx.act, LRELU_SLOPE, g.dsee_amax)
-        elif ctx.act != L.ACT_NONE:
-            g = torch.empty_like(dy)
-            L.call("act_bwd", dy, out, g, C.c_long(dy.numel()), ctx.act, LRELU_SLOPE)
-        else:
-            g = dy
-        dx = dw = db = dres = None
-        fused = (ctx.wino and P().winograd_wgrad and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
-                 and _wgrad_mode(geom.Cin, geom.Cout) != 1 and _adjoint_ok(geom.Cout, geom.Cin))
-        sums = None
-        if ctx.wino and P().winograd_wgrad and ctx.needs_input_grad[1]:
-            want = {"bias": bool(ctx.has_bias and ctx.needs_input_grad[2]),
-                    "n0": ctx.noise if (ctx.noise is not None and ctx.needs_input_grad[8]) else None,
-                    "n1": ctx.res_noise if (ctx.res_noise is not None and ctx.needs_input_grad[10]) else None}
-            nb_w = _wino_chunk(geom.N, geom.Hi, geom.Wi, max(geom.Cin, geom.Cout))
-            if (want["bias"] or want["n0"] is not None or want["n1"] is not None) and \
-                    _dout_sums_ok(geom.N, nb_w, geom.Cout, _wgrad_mode(geom.Cin, geom.Cout)):
-                sums = want
-        # the 27-output 1x1 GEMM of the to-RGB layer (conv2d's thin path): both gradients laid out along the input channels
-        thin1 = (P().thin_gemm and kh == 1 and kw == 1 and geom.ups == 0 and co <= 32 and ci == geom.Cin and not ctx.has_res
-                 and geom.Ho == geom.Hi and geom.Wo == geom.Wi and geom.Cin >= 128)
-        if thin1:
-            m = geom.N * geom.Hi * geom.Wi
-            if ctx.needs_input_grad[0]:
-                dx = torch.empty_like(x)
-            if ctx.needs_input_grad[1]:
-                dw = new(co, ci, 1, 1)
-            ws = scratch(L.lib().dsee_thin1x1_bwd_workspace(geom.Cin, co), "wgrad") if dw is not None else None
-            da = None
-            if dx is not None and ctx.in_act:
-                da = amax_slot()       # (x = LeakyReLU(.) of a producer that deferred its activation's backward to this kernel)
-                tag_amax(dx, da)
-            L.call("thin1x1_bwd", g, geom.Cout, w, x, dx, dw, C.c_long(m), geom.Cin, co, ws, int(da is not None), LRELU_SLOPE, da)
-        elif fused:
-            # one A dY A^T transform of g serves the weight gradient AND (adjoint form) the data gradient
-            dw, dx = _wino_wgrad(x, g, geom.N, geom.Hi, geom.Wi, geom.Cin, geom.Cout, co, ci, vkeep, w_for_dx=w, sums=sums)
-        elif ctx.needs_input_grad[0] and ctx.wino:
-            dx = _wino_conv(g, w, geom.N, geom.Ho, geom.Wo, geom.Cin, geom.Cout, True)
-        elif ctx.needs_input_grad[0] and not thin1 and _s2_parity_ok(geom, kh, kw):
-            dx = _dgrad_stride2_parity(g, w, geom, ci, amax_cache=getattr(ctx, "amax_cache", None), exact=ctx.exact)
-        elif ctx.needs_input_grad[0] and not thin1:
-            gd = L.geom_dgrad(geom)
-            dxl = conv_raw(g, _pack_dgrad(w, geom.Cout, gd.korder), gd, amax_cache=getattr(ctx, "amax_cache", None),
-                           exact=ctx.exact)
-            if geom.ups:
-                dx = torch.empty_like(x)
-                L.call("sumpool", dxl, dx, geom.N, gd.Ho, gd.Wo, geom.Cin, geom.ups)
-            else:
-                dx = dxl
-        if dw is not None or thin1:
-            pass
-        elif ctx.needs_input_grad[1] and ctx.thin:
-            ws = scratch(L.lib().dsee_conv3x3_thin_wgrad_workspace(geom.Cin), "wgrad")
-            dw = new(co, ci, 3, 3)
-            L.call("conv3x3_thin_wgrad", x, g, ws, dw, geom.N, geom.Hi, geom.Wi, geom.Cin, co, ci)
-        elif ctx.needs_input_grad[1] and ctx.wino and P().winograd_wgrad:
-            dw = _wino_wgrad(x, g, geom.N, geom.Hi, geom.Wi, geom.Cin, geom.Cout, co, ci, vkeep, sums=sums)
-        elif ctx.needs_input_grad[1]:
-            dw = wgrad_raw(x, g, geom, co, ci, kh, kw, amax_cache=getattr(ctx, "amax_cache", None), exact=ctx.exact)
-        if ctx.reflect:
-            # the border terms of the reflection padding, added in place to what the zero-padded paths above produced
-            if dx is not None:
-                assert dx.is_contiguous()
-                L.call("reflect_ring_dgrad", g, w, dx, geom.N, geom.Hi, geom.Wi, ci, geom.Cin, co, geom.Cout)
-                dx.dsee_amax = None
-            if dw is not None:
-                assert dw.is_contiguous()
-                nbytes = L.lib().dsee_reflect_ring_wgrad_workspace(geom.N, geom.Hi, geom.Wi, ci, co)
-                L.call("reflect_ring_wgrad", x, g, scratch(nbytes, "ringw"), C.c_size_t(nbytes), dw, geom.N, geom.Hi, geom.Wi,
-                       ci, geom.Cin, co, geom.Cout)
-        if sums is not None and sums.get("dbias") is not None:
-            db = sums["dbias"][:co]
-        elif ctx.has_bias and ctx.needs_input_grad[2]:
-            db = channel_dot(g, None, co).clone()
-        if ctx.has_res and ctx.needs_input_grad[3]:
-            if ctx.res_sink is not None:
-                ctx.res_sink.put(g)      # picked up as the `add` operand of the norm backward that also feeds on `res`
-            else:
-                dres = g
-
-        def noise_wgrad(eps):
-            cn = g.shape[-1]
-            mrows = g.numel() // cn
-            d = new(cn)
-            L.call("channel_dot_rng", g, d, mrows, cn, scratch(L.lib().dsee_channel_dot_workspace(mrows, cn), "chdot"),
-                   eps.seed, eps.offset)
-            return d
-
-        if sums is not None and "dn0" in sums:
-            dnw, drnw = sums["dn0"], sums["dn1"]
-        else:
-            dnw = noise_wgrad(ctx.noise) if (ctx.noise is not None and ctx.needs_input_grad[8]) else None
-            drnw = noise_wgrad(ctx.res_noise) if (ctx.res_noise is not None and ctx.needs_input_grad[10]) else None
-        if ctx.in_act and dx is not None and not thin1:
-            # (any other kernel path of a layer under the `in_act` contract: the deferred LeakyReLU backward as its own pass)
-            gx = torch.empty_like(dx)
-            tag_amax(gx, amax_slot())
-            L.call("act_bwd_amax", dx.contiguous(), x, gx, C.c_long(dx.numel()), ctx.in_act, LRELU_SLOPE, gx.dsee_amax)
-            dx = gx
-        return dx, dw, db, dres, None, None, None, None, dnw, None, drnw, None, None, None, None, None, None, None
+        spec, path, geom, need = ctx.spec, ctx.path, ctx.geom, ctx.needs_input_grad
+        g = _act_bwd(dy.contiguous(), out, spec.act, path.g_amax, spec.defer_act_bwd)
+        want = {"bias": bool(ctx.has_bias and need[IN_BIAS]), "res": bool(ctx.has_res and need[IN_RES]),
+                "n0": ctx.noise if need[IN_NOISE_W] else None, "n1": ctx.res_noise if need[IN_RES_NOISE_W] else None}
+        sums = want if (path.dout_sums and (want["bias"] or want["n0"] is not None or want["n1"] is not None)) else None
+        dx, dw = _conv_grads(path, x, w, g, geom, vkeep, sums, spec.in_act, dict(amax_cache=ctx.amax_cache, exact=spec.exact))
+        if spec.reflect:
+            _reflect_border_grads(x, w, g, dx, dw, geom)
+        db, dres, dnw, drnw = _conv_side_grads(g, w.shape[0], want, sums, spec.res_sink)
+        if spec.in_act and dx is not None and path.dgrad != THIN1:
+            dx = _act_bwd(dx.contiguous(), x, spec.in_act, True)    # the LeakyReLU backward x's producer deferred, as a pass
+        return dx, dw, db, dres, dnw, drnw, None
 
 
 class GradSink:
@@ -1138,7 +1146,6 @@ class GradSink:
     the residual's gradient here instead of returning it, and the backward of the normalisation that ALSO consumes `x`
     (it runs later: its own incoming gradient depends on that convolution's data gradient) adds it to its dx in the
     same pass -- the autograd engine's separate fan-in addition (3 full-tensor passes) never runs.
-
 
     A sink lives for ONE forward/backward pair (the resblock creates a new one per forward) and only full backward passes
     are supported: a partial backward that runs the convolution's node but not the norm's (torch.autograd.grad with
@@ -1215,30 +1222,27 @@ def conv2d(x, w, bias=None, res=None, stride=1, pad=1, ups=0, act=L.ACT_NONE, no
     `res_sink` (GradSink): the residual's gradient is handed to the norm backward instead of the autograd engine.
     `stats`: the output feeds a training-mode BatchNorm -- a Winograd layer then writes the statistics rows in its output
     transform (bn_stats finds them on the tensor).
-    `in_act` / `defer_act_bwd`: see Conv2d.forward (x is the LeakyReLU output of a layer called with defer_act_bwd).
-    `reflect`: reflection padding instead of zero padding (Conv2d.forward)."""
-    if not (torch.is_grad_enabled() and x.requires_grad):
-        in_act = 0
+    `in_act` / `defer_act_bwd` (x is the LeakyReLU output of a layer called with defer_act_bwd), `reflect`: see Conv2d.forward."""
+    in_act = int(in_act or 0) if (torch.is_grad_enabled() and x.requires_grad) else 0
     if reflect:
         assert noise is None and res_noise is None and res is None and act == L.ACT_NONE
-        return Conv2d.apply(x, w, bias, None, stride, pad, ups, act, None, None, None, None, None, False, False, 0, False, True)
+        return Conv2d.apply(x, w, bias, None, None, None, ConvSpec(stride=stride, pad=pad, ups=ups, act=act, reflect=True))
     if _thin_ok(x, w, res, stride, pad, ups, noise, res_noise):
-        co, ci = w.shape[0], w.shape[1]
-        kh, kw = w.shape[2], w.shape[3]
+        co, ci, kh, kw = w.shape
         w27 = w.permute(2, 3, 0, 1).reshape(kh * kw * co, ci, 1, 1)    # row tap*co_n + co (55 KB of parameter glue)
-        z = Conv2d.apply(x, w27, None, None, 1, 0, 0, L.ACT_NONE, None, None, None, None, None, True, False, in_act)
+        z = Conv2d.apply(x, w27, None, None, None, None, ConvSpec(stride=1, pad=0, exact=True, in_act=in_act))
         return ThinGather.apply(z, bias, co, act, kh, kw, pad)
     if res_noise is not None and not _fusable_noise(x, w, stride, pad, ups, res_noise[1]):
         # (the shortcut's own node must see its gradient: no sink)
         res, res_noise, res_sink = UpNoise.apply(res, res_noise[0], res_noise[1], 0), None, None
     rn = (None, None) if res_noise is None else res_noise
+    spec = ConvSpec(stride=stride, pad=pad, ups=ups, act=act, res_noise_eps=rn[1], res_sink=res_sink, in_act=in_act)
     if noise is None or (_fusable_noise(x, w, stride, pad, ups, noise[1]) and act == L.ACT_NONE):
         nz = (None, None) if noise is None else noise
-        return Conv2d.apply(x, w, bias, res, stride, pad, ups, act, nz[0], nz[1], rn[0], rn[1], res_sink, False, bool(stats),
-                            in_act, defer_act_bwd)
+        spec = spec._replace(noise_eps=nz[1], stats=bool(stats), defer_act_bwd=bool(defer_act_bwd))
+        return Conv2d.apply(x, w, bias, res, nz[0], rn[0], spec)
     assert not defer_act_bwd
-    y = Conv2d.apply(x, w, bias, res, stride, pad, ups, act, None, None, rn[0], rn[1], res_sink, False, False, in_act)
-    return UpNoise.apply(y, noise[0], noise[1], 0)
+    return UpNoise.apply(Conv2d.apply(x, w, bias, res, None, rn[0], spec), noise[0], noise[1], 0)
 
 
 # ------------------------------------------------------------------------------------ spectral norm
@@ -1558,11 +1562,7 @@ class UpNoise(torch.autograd.Function):
             else:
                 dx = dy
         if ctx.philox is not None and ctx.needs_input_grad[1]:
-            m = dy.numel() // c
-            ws = scratch(L.lib().dsee_channel_dot_workspace(C.c_long(m), c), "chdot")
-            dw = new(c)
-            L.call("channel_dot_rng", dy, dw, C.c_long(m), c, ws, C.c_uint64(ctx.philox.seed),
-                   C.c_uint64(ctx.philox.offset))
+            dw = _noise_wgrad(dy, ctx.philox)
         elif eps is not None and ctx.needs_input_grad[1]:
             dw = channel_dot(dy, eps, c).clone()
         return dx, dw, None, None, None
@@ -1940,7 +1940,7 @@ def modulate_bwd(dh, out, x, scale, mean, invstd, rows, cfg, as_dm=False, add=No
 def _norm_product_direct(geom, cat, w, table, ca, b2, x, mean, invstd, out, scale, add_one):
     """out = lrelu(norm(x) * (gamma + add_one) + beta), (gamma | beta) = conv3x3(cat, w (+ per-image `table` over the one-hot
     channels behind the first `ca`)) + b2 formed in the epilogue of the direct convolution kernel"""
-    wp = _pack_fwd(w, w.shape[1], geom.korder) if w is not None else None
+    wp = _pack("fwd", w, w.shape[1], geom.korder) if w is not None else None
     with _timed(_variant(geom, True), _flops(geom)):
         _call_sg("conv2d_modulate_fwd", stat_groups(mean),
                  (C.byref(geom), cat, wp, table, ca, b2.contiguous(), x, mean, invstd, out, scale, x.shape[3]),
@@ -1987,7 +1987,7 @@ class SpadeNormAct(torch.autograd.Function):
         dcat = dw2 = db2 = None
         if ctx.needs_input_grad[1]:
             gd = L.geom_dgrad(geom)
-            dcl = conv_raw(dgb, _pack_dgrad(w2, rows, gd.korder), gd)
+            dcl = conv_raw(dgb, _pack("dgrad", w2, rows, gd.korder), gd)
             if geom.ups:
                 dcat = torch.empty_like(cat)
                 L.call("sumpool", dcl, dcat, n, gd.Ho, gd.Wo, kin, geom.ups)
@@ -2169,7 +2169,7 @@ def _embedding_dgrad(dgb, w2a, cat, rows, has_t, wino):
     if wino and _wino_chunk(n, h, w, rows) is not None:
         return _wino_conv(dgb, w2a, n, h, w, NHIDDEN, rows, True, None, res, act, res_ld=res_ld)
     ga = L.ConvGeom(n, h, w, rows, h, w, NHIDDEN, 3, 3, 1, 1, -1, 0, 0, 1)
-    return conv_raw(dgb, _pack_dgrad(w2a, rows, 1), ga, None, res, act, res_ld=res_ld)
+    return conv_raw(dgb, _pack("dgrad", w2a, rows, 1), ga, None, res, act, res_ld=res_ld)
 
 
 def _mlp_shared_grad(dactv, cat, cat_amax, actv_low, cat_ups, lab, shift, has_t):

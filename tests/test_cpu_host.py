@@ -755,3 +755,195 @@ def test_operand_survives_an_autograd_context():
     ctx = Ctx()
     ops.save_with_operand(ctx, None, a)
     assert ops.saved_with_operand(ctx) == ([a], None)
+
+
+# (n, hi, wi, cin_s, cout_s, co, ci, kh, kw, stride, pad, ups, has_res, exact): every distinct convolution of one G + D step of
+# the 32 -> 256, ngf = 16 model at batch 2 (generator, encoder with its ups = 1 layer, both discriminator scales at batch 2 and
+# 4, the VGG taps), under the default plan and under thin_gemm=False (to-RGB and D's last layer in their 1 x 1 and k x k forms)
+F, T = False, True
+STEP_CONVS = [
+    (2, 16, 16, 512, 512, 512, 512, 3, 3, 1, 1, 0, F, F), (2, 17, 17, 128, 256, 256, 128, 4, 4, 1, 2, 0, F, F),
+    (2, 18, 18, 256, 4, 1, 256, 4, 4, 1, 2, 0, F, F), (2, 18, 18, 256, 16, 16, 256, 1, 1, 1, 0, 0, F, T),
+    (2, 32, 32, 4, 32, 32, 3, 3, 3, 1, 1, 0, F, F), (2, 32, 32, 4, 256, 256, 3, 3, 3, 1, 1, 0, F, F),
+    (2, 32, 32, 32, 64, 64, 32, 3, 3, 1, 1, 0, F, F), (2, 32, 32, 64, 128, 128, 64, 3, 3, 1, 1, 0, F, F),
+    (2, 32, 32, 128, 256, 256, 128, 3, 3, 1, 1, 1, F, F), (2, 32, 32, 256, 256, 256, 256, 3, 3, 1, 1, 0, F, F),
+    (2, 32, 32, 256, 256, 256, 256, 3, 3, 1, 1, 0, T, F), (2, 32, 32, 256, 512, 512, 256, 3, 3, 1, 1, 0, F, F),
+    (2, 32, 32, 512, 512, 512, 512, 3, 3, 1, 1, 0, F, F), (2, 33, 33, 64, 128, 128, 64, 4, 4, 2, 2, 0, F, F),
+    (2, 33, 33, 128, 256, 256, 128, 4, 4, 1, 2, 0, F, F), (2, 34, 34, 256, 4, 1, 256, 4, 4, 1, 2, 0, F, F),
+    (2, 34, 34, 256, 16, 16, 256, 1, 1, 1, 0, 0, F, T), (2, 64, 64, 128, 256, 256, 128, 3, 3, 1, 1, 0, F, F),
+    (2, 64, 64, 128, 256, 256, 128, 3, 3, 1, 1, 1, F, F), (2, 64, 64, 256, 128, 128, 256, 3, 3, 1, 1, 0, F, F),
+    (2, 64, 64, 256, 256, 256, 256, 3, 3, 1, 1, 0, F, F), (2, 64, 64, 256, 256, 256, 256, 3, 3, 1, 1, 0, T, F),
+    (2, 65, 65, 32, 64, 64, 32, 4, 4, 2, 2, 0, F, F), (2, 65, 65, 64, 128, 128, 64, 4, 4, 2, 2, 0, F, F),
+    (2, 128, 128, 24, 32, 32, 22, 4, 4, 2, 2, 0, F, F), (2, 128, 128, 64, 128, 128, 64, 3, 3, 1, 1, 0, F, F),
+    (2, 128, 128, 64, 128, 128, 64, 3, 3, 2, 1, 0, F, F), (2, 128, 128, 128, 128, 128, 128, 3, 3, 1, 1, 0, F, F),
+    (2, 128, 128, 256, 128, 128, 256, 3, 3, 1, 1, 0, F, F), (2, 128, 128, 256, 256, 256, 256, 3, 3, 1, 1, 0, F, F),
+    (2, 128, 128, 256, 256, 256, 256, 3, 3, 1, 1, 0, T, F), (2, 129, 129, 32, 64, 64, 32, 4, 4, 2, 2, 0, F, F),
+    (2, 256, 256, 4, 32, 32, 3, 3, 3, 1, 1, 0, F, F), (2, 256, 256, 4, 64, 64, 3, 3, 3, 1, 1, 0, F, F),
+    (2, 256, 256, 24, 32, 32, 22, 4, 4, 2, 2, 0, F, F), (2, 256, 256, 32, 64, 64, 32, 3, 3, 2, 1, 0, F, F),
+    (2, 256, 256, 64, 64, 64, 64, 3, 3, 1, 1, 0, F, F), (2, 256, 256, 256, 4, 3, 256, 3, 3, 1, 1, 0, F, F),
+    (2, 256, 256, 256, 28, 27, 256, 1, 1, 1, 0, 0, F, T), (2, 256, 256, 256, 256, 256, 256, 3, 3, 1, 1, 0, F, F),
+    (2, 256, 256, 256, 256, 256, 256, 3, 3, 1, 1, 0, T, F), (4, 17, 17, 128, 256, 256, 128, 4, 4, 1, 2, 0, F, F),
+    (4, 18, 18, 256, 4, 1, 256, 4, 4, 1, 2, 0, F, F), (4, 18, 18, 256, 16, 16, 256, 1, 1, 1, 0, 0, F, T),
+    (4, 33, 33, 64, 128, 128, 64, 4, 4, 2, 2, 0, F, F), (4, 33, 33, 128, 256, 256, 128, 4, 4, 1, 2, 0, F, F),
+    (4, 34, 34, 256, 4, 1, 256, 4, 4, 1, 2, 0, F, F), (4, 34, 34, 256, 16, 16, 256, 1, 1, 1, 0, 0, F, T),
+    (4, 65, 65, 32, 64, 64, 32, 4, 4, 2, 2, 0, F, F), (4, 65, 65, 64, 128, 128, 64, 4, 4, 2, 2, 0, F, F),
+    (4, 128, 128, 24, 32, 32, 22, 4, 4, 2, 2, 0, F, F), (4, 129, 129, 32, 64, 64, 32, 4, 4, 2, 2, 0, F, F),
+    (4, 256, 256, 24, 32, 32, 22, 4, 4, 2, 2, 0, F, F),
+]
+# ... and what that step does not hold: the bs = 8 flagship's 512 -> 512 layer (weight-gradient mode 2, channel sums in the
+# A dY A^T pass) and its to-RGB layer in both forms, a 3 x 3 layer whose height is no multiple of 4, one with a residual that
+# Winograd does not take, an odd-sized 4 x 4 / stride 2 layer under an upsampling, a 1 x 1 layer too narrow for the thin kernel
+EXTRA_CONVS = [
+    (8, 64, 64, 512, 512, 512, 512, 3, 3, 1, 1, 0, F, F), (8, 64, 64, 512, 512, 512, 512, 3, 3, 1, 1, 0, T, F),
+    (8, 256, 256, 512, 28, 27, 512, 1, 1, 1, 0, 0, F, T), (8, 256, 256, 512, 4, 3, 512, 3, 3, 1, 1, 0, F, F),
+    (2, 30, 32, 256, 256, 256, 256, 3, 3, 1, 1, 0, F, F), (2, 32, 32, 64, 64, 64, 64, 3, 3, 1, 1, 0, T, F),
+    (2, 33, 35, 64, 128, 128, 64, 4, 4, 2, 2, 1, F, F), (2, 32, 32, 64, 16, 16, 64, 1, 1, 1, 0, 0, F, F),
+    (2, 32, 32, 128, 16, 16, 126, 1, 1, 1, 0, 0, F, T), (2, 32, 32, 128, 16, 16, 128, 1, 1, 1, 0, 0, T, F),
+]
+
+
+def test_conv_path_matches_the_predicates_it_replaced():
+    """ops._conv_path names, once per layer, the kernel families that Conv2d.forward (ctx.wino, ctx.thin, the kept V) and
+    Conv2d.backward (thin1, fused, the dx and the dw ladder, the three copies of the activation backward, the `sums` condition)
+    derived in five places: the same answer on every convolution of the 32 -> 256 step and on the shapes that step lacks, under
+    the default plan and with each switch that those predicates read flipped, for all four (x, w) gradient needs."""
+    from deepsee_amd import lib as L, ops, plan as PL
+
+    def old(n, hi, wi, cin_s, cout_s, co, ci, kh, kw, stride, pad, ups, has_res, exact, need_dx, need_dw):
+        P = ops.P
+        geom = L.geom_fwd(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
+        # forward
+        wino = ops._wino_ok(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
+        thin = (not P().thin_gemm and kh == 3 and stride == 1 and pad == 1 and ups == 0 and co <= 4 and cin_s % 256 == 0
+                and cin_s <= 1024 and wi % 64 == 0 and not has_res)
+        fwd = "thin3" if thin else "wino" if wino else "direct"
+        keep_v = bool(not thin and wino and P().keep_v and need_dw and ops._wgrad_mode(cin_s, cout_s) == 2)
+        # backward: the activation's branch that attached a maximum
+        g_amax = bool((wino and P().presplit_dm) or (not wino and ops._direct_split_on(exact) and P().conv_amax_out))
+        fused = (wino and P().winograd_wgrad and need_dx and need_dw
+                 and ops._wgrad_mode(geom.Cin, geom.Cout) != 1 and ops._adjoint_ok(geom.Cout, geom.Cin))
+        dout_sums = False
+        if wino and P().winograd_wgrad and need_dw:
+            nb_w = ops._wino_chunk(geom.N, geom.Hi, geom.Wi, max(geom.Cin, geom.Cout))
+            dout_sums = bool(ops._dout_sums_ok(geom.N, nb_w, geom.Cout, ops._wgrad_mode(geom.Cin, geom.Cout)))
+        thin1 = (P().thin_gemm and kh == 1 and kw == 1 and geom.ups == 0 and co <= 32 and ci == geom.Cin and not has_res
+                 and geom.Ho == geom.Hi and geom.Wo == geom.Wi and geom.Cin >= 128)
+        dx = dw = None
+        if thin1:
+            dx, dw = ("thin1" if need_dx else None), ("thin1" if need_dw else None)
+        elif fused:
+            dw, dx = "wino", "adjoint"
+        elif need_dx and wino:
+            dx = "wino"
+        elif need_dx and not thin1 and ops._s2_parity_ok(geom, kh, kw):
+            dx = "s2_parity"
+        elif need_dx and not thin1:
+            dx = "direct_sumpool" if geom.ups else "direct"
+        if dw is not None or thin1:
+            pass
+        elif need_dw and thin:
+            dw = "thin3"
+        elif need_dw and wino and P().winograd_wgrad:
+            dw = "wino"
+        elif need_dw:
+            dw = "direct"
+        return (fwd, dx, dw, keep_v, g_amax, dout_sums)
+
+    assert (ops.THIN3, ops.WINO, ops.DIRECT, ops.THIN1, ops.ADJOINT, ops.S2_PARITY, ops.DIRECT_SUMPOOL) == \
+        ("thin3", "wino", "direct", "thin1", "adjoint", "s2_parity", "direct_sumpool")
+    flips = ["winograd", "winograd_wgrad", "thin_gemm", "gemm_split", "gemm_af32", "adjoint_dgrad", "dgrad_s2_parity", "half",
+             "keep_v", "presplit_dm", "conv_amax_out", "dout_sums", "gemm_f16x2"]
+    plans = [PL.DEFAULT_PLAN] + [PL.DEFAULT_PLAN.replace(**{f: not getattr(PL.DEFAULT_PLAN, f)}) for f in flips]
+    plans.append(PL.DEFAULT_PLAN.replace(conv_f16x2_min_flop=0.0))
+    seen = {"fwd": set(), "dgrad": set(), "wgrad": set(), "flags": set()}
+    for plan in plans:
+        with plan.active():
+            for shape in STEP_CONVS + EXTRA_CONVS:
+                for need_dx in (False, True):
+                    for need_dw in (False, True):
+                        got = ops._conv_path(*shape, need_dx, need_dw)
+                        assert isinstance(got, ops.ConvPath) and tuple(got) == old(*shape, need_dx, need_dw), \
+                            (plan, shape, need_dx, need_dw, got)
+                        seen["fwd"].add(got.fwd), seen["dgrad"].add(got.dgrad), seen["wgrad"].add(got.wgrad)
+                        seen["flags"].add((got.keep_v, got.g_amax, got.dout_sums))
+    assert ops.P() is PL.DEFAULT_PLAN
+    # the grid reaches every family the record can name, and both values of every flag
+    assert seen["fwd"] == {"thin3", "wino", "direct"}
+    assert seen["dgrad"] == {None, "thin1", "adjoint", "wino", "s2_parity", "direct", "direct_sumpool"}
+    assert seen["wgrad"] == {None, "thin1", "thin3", "wino", "direct"}
+    assert all({f[i] for f in seen["flags"]} == {False, True} for i in range(3))
+    with pytest.raises(AttributeError):
+        got.fwd = "wino"                                  # frozen
+
+
+def test_conv2d_hands_every_setting_to_the_node_in_one_spec(monkeypatch):
+    """ops.conv2d -> Conv2d.apply(x, w, bias, res, noise_w, res_noise_w, ConvSpec): every non-tensor setting conv2d can set arrives
+    in the spec, on each of its four routes (reflect, the thin 27-output split, fused noise, the UpNoise fallbacks); the named
+    positions into needs_input_grad are the node's inputs, one gradient each.  No device: the nodes are replaced by recorders."""
+    import inspect
+    from deepsee_amd import lib as L, ops
+    calls = []
+    monkeypatch.setattr(ops.Conv2d, "apply", lambda *a: calls.append(("conv",) + a) or "y")
+    monkeypatch.setattr(ops.UpNoise, "apply", lambda *a: calls.append(("upnoise",) + a) or "up")
+    monkeypatch.setattr(ops.ThinGather, "apply", lambda *a: calls.append(("gather",) + a) or "rgb")
+
+    inputs = list(inspect.signature(ops.Conv2d.forward).parameters)[1:]
+    named = [k for k in vars(ops) if k.startswith("IN_")]
+    assert inputs == ["x", "w", "bias", "res", "noise_w", "res_noise_w", "spec"]
+    assert [k[3:].lower() for k in sorted(named, key=lambda k: getattr(ops, k))] == inputs
+    assert sorted(getattr(ops, k) for k in named) == list(range(len(inputs)))
+    assert ops.ConvSpec._fields == ("stride", "pad", "ups", "act", "noise_eps", "res_noise_eps", "res_sink", "exact", "stats",
+                                    "in_act", "defer_act_bwd", "reflect")
+    assert ops.ConvSpec() == (1, 1, 0, L.ACT_NONE, None, None, None, False, False, 0, False, False)
+    with pytest.raises(AttributeError):
+        ops.ConvSpec().stride = 2                         # frozen
+
+    x = torch.zeros(2, 32, 32, 256, requires_grad=True)
+    w, b, res = torch.zeros(256, 256, 3, 3), torch.zeros(256), torch.zeros(2, 32, 32, 256)
+    nw, rnw, sink = torch.zeros(256), torch.ones(256), ops.GradSink()
+    eps, reps = ops.PhiloxNormal((2, 32, 32, 256), 5, 64), ops.PhiloxNormal((2, 32, 32, 256), 6, 128)
+
+    # every keyword at once, on the route that fuses both noises: one node, no UpNoise
+    assert ops.conv2d(x, w, b, res, stride=1, pad=1, ups=0, act=L.ACT_NONE, noise=(nw, eps), res_noise=(rnw, reps), res_sink=sink,
+                      stats=1, in_act=L.ACT_LRELU) == "y"
+    (kind, *args), = calls
+    assert kind == "conv" and len(args) == len(inputs)
+    assert all(a is e for a, e in zip(args[:6], (x, w, b, res, nw, rnw)))
+    assert args[6] == ops.ConvSpec(1, 1, 0, L.ACT_NONE, eps, reps, sink, False, True, L.ACT_LRELU, False, False)
+    assert args[6].noise_eps is eps and args[6].res_noise_eps is reps and args[6].res_sink is sink and args[6].stats is True
+    calls.clear()
+    ops.conv2d(x, w, b, None, stride=2, pad=0, ups=1, act=L.ACT_LRELU, defer_act_bwd=True)
+    assert calls == [("conv", x, w, b, None, None, None, ops.ConvSpec(2, 0, 1, L.ACT_LRELU, defer_act_bwd=True))]
+    calls.clear()
+    # `in_act` is reset where nothing will differentiate x
+    ops.conv2d(x.detach(), w, in_act=L.ACT_LRELU)
+    with torch.no_grad():
+        ops.conv2d(x, w, in_act=L.ACT_LRELU)
+    assert [c[-1].in_act for c in calls] == [0, 0]
+    calls.clear()
+    # reflect: a plain layer, nothing else set
+    ops.conv2d(x, w, b, reflect=True, in_act=L.ACT_LRELU)
+    assert calls == [("conv", x, w, b, None, None, None, ops.ConvSpec(1, 1, 0, L.ACT_NONE, reflect=True))]
+    for bad in (dict(res=res), dict(act=L.ACT_LRELU), dict(noise=(nw, eps)), dict(res_noise=(rnw, reps))):
+        with pytest.raises(AssertionError):
+            ops.conv2d(x, w, b, reflect=True, **bad)
+    calls.clear()
+    # the thin split: 27 outputs of a 1 x 1 layer kept exact, then the gather with the bias and the activation
+    w3 = torch.zeros(3, 256, 3, 3)
+    assert ops.conv2d(x, w3, b[:3], act=L.ACT_TANH, in_act=L.ACT_LRELU) == "rgb"
+    (_, cx, w27, *rest), gather = calls
+    assert cx is x and tuple(w27.shape) == (27, 256, 1, 1) and rest[:4] == [None] * 4
+    assert rest[4] == ops.ConvSpec(1, 0, 0, L.ACT_NONE, exact=True, in_act=L.ACT_LRELU)
+    assert gather[0] == "gather" and gather[1] == "y" and gather[3:] == (3, L.ACT_TANH, 3, 3, 1)
+    calls.clear()
+    # a noise that cannot ride in the output transform runs as UpNoise: a replayed tensor behind the layer, a residual noise
+    # on a layer Winograd does not take (its shortcut then keeps its own node: no sink)
+    teps = torch.zeros(2, 32, 32, 256)
+    assert ops.conv2d(x, w, b, res, noise=(nw, teps), res_noise=(rnw, reps), res_sink=sink, stats=True, in_act=L.ACT_LRELU) == "up"
+    assert calls == [("conv", x, w, b, res, None, rnw, ops.ConvSpec(res_noise_eps=reps, res_sink=sink, in_act=L.ACT_LRELU)),
+                     ("upnoise", "y", nw, teps, 0)]
+    with pytest.raises(AssertionError):
+        ops.conv2d(x, w, b, noise=(nw, teps), act=L.ACT_LRELU, defer_act_bwd=True)
+    calls.clear()
+    ops.conv2d(x, w, b, res, stride=2, res_noise=(rnw, reps), res_sink=sink)
+    assert calls == [("upnoise", res, rnw, reps, 0), ("conv", x, w, b, "up", None, None, ops.ConvSpec(stride=2))]

@@ -19,7 +19,7 @@ for (n, r, c) in [(8, 256, 512), (8, 128, 512), (8, 64, 512), (8, 32, 512)]:
     ys = ops._wino_conv(x, w, n, r, r, c, c, False)
     print("R=%d: winograd bf16x3 %.3f ms (%.0f TF/s algorithmic) | rel diff vs f32 mfma %.2e" % (r, ts, 2.0 * n * r * r * c * 9 * c / ts / 1e9, ((ys - yf).norm() / yf.norm()).item()))
     geom = L.geom_fwd(n, r, r, c, c, 3, 1, 1)
-    wp = ops._pack_fwd(w, c, 1)
+    wp = ops._pack("fwd", w, c, 1)
     td = timeit(lambda: ops.conv_raw(x, wp, geom))
     fl = 2.0 * n * r * r * c * 9 * c
     print("R=%d: winograd %.3f ms (%.0f TF/s algorithmic) | direct halo %.3f ms (%.0f TF/s)" % (r, tw, fl / tw / 1e9, td, fl / td / 1e9))

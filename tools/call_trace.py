@@ -5,8 +5,9 @@ too: the byte count of every workspace-size query it is fed with, and its tag, i
 
 The scenario is the one() of tests/test_gpu_model.py::test_kernel_path_switches (batchSize=2, ngf=16, seed=3: one G step and one
 D step from recipe_state, hip_graphs=False) under the default plan, under every entry of that file's SWITCHES, and with
-precision="fp16" with half_norms on and off.  The default-plan and the 16-bit scenarios also get a SHA-256 over the generated
-image, every loss and every G and D parameter gradient.
+precision="fp16" with half_norms on and off, and with netG="nospadenostyle" (the reflection border pass and InstNormRes, which the
+default generator never runs) in both precisions.  The default-plan, the 16-bit and the nospadenostyle scenarios also get a SHA-256
+over the generated image, every loss and every G and D parameter gradient.
 
     python tools/call_trace.py --out DIR [--scenarios default keep_v=False fp16 ...]    # one <scenario>.trace per scenario + index.json
     python tools/call_trace.py --compare DIR_A DIR_B [--again DIR_A2]                   # the table of profiles/ops_operand_refactor.md
@@ -25,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.append(ROOT)       # (appended: a PYTHONPATH that names another checkout's package wins)
 
-HASHED = ("default", "fp16", "fp16_two_term_norms")
+HASHED = ("default", "fp16", "fp16_two_term_norms", "nospadenostyle", "nospadenostyle_fp16")
 DTYPES = {"torch.float32": "f32", "torch.float16": "f16", "torch.int16": "i16", "torch.int32": "i32", "torch.uint8": "u8",
           "torch.int64": "i64", "torch.bfloat16": "bf16", "torch.float64": "f64"}
 
@@ -72,7 +73,8 @@ class Recorder:
 
 
 def scenarios():
-    """[(name, make_opt overrides)]: default, every SWITCHES entry (tests/test_gpu_model.py), the two 16-bit modes."""
+    """[(name, make_opt overrides)]: default, every SWITCHES entry (tests/test_gpu_model.py), the two 16-bit modes, the resnet
+    generator in both precisions."""
     from deepsee_amd import ops
     from tests.test_gpu_model import SWITCHES
     out = [("default", {})]
@@ -82,6 +84,8 @@ def scenarios():
         out.append(("%s=%s" % (name, value), dict(kernel_plan={name: value})))
     out.append(("fp16", dict(precision="fp16", kernel_plan=dict(half_norms=True))))
     out.append(("fp16_two_term_norms", dict(precision="fp16", kernel_plan=dict(half_norms=False))))
+    out.append(("nospadenostyle", dict(netG="nospadenostyle")))
+    out.append(("nospadenostyle_fp16", dict(netG="nospadenostyle", precision="fp16")))
     return out
 
 
@@ -92,6 +96,10 @@ def run(extra, hashed):
     from deepsee_amd.managers import TrainerManager
     from deepsee_amd.options import make_opt
     over = dict(batchSize=2, ngf=16, seed=3)
+    if "netG" in extra:
+        from tools.gen_golden_ablation import install_ablation
+        install_ablation()          # (recipe_state in the state layout of the ablation generators; 'deepsee' keeps the oracle's own)
+        over["netG"] = extra["netG"]
     batch = O.synthetic_batch(O.make_opt(**over), 2, seed=77)
     states = O.recipe_state(O.make_opt(**over), gain=1.0)
     tm = TrainerManager(make_opt(hip_graphs=False, **dict(over, **extra)))

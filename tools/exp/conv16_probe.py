@@ -19,7 +19,7 @@ cases = [("64->64 k3 @256^2 N8", 8, 256, 64, 64, 3, 1, 1, 0), ("64->128 k3 @128^
 for name, n, h, ci, co, k, s, p, ups in cases:
     x = torch.randn(n, h, h, ci, generator=g).cuda(); w = (torch.randn(co, ci, k, k, generator=g) / (ci * k * k) ** 0.5).cuda()
     geom = L.geom_fwd(n, h, h, ci, co, k, s, p, ups)
-    wp = ops._pack_fwd(w, ci, geom.korder)
+    wp = ops._pack("fwd", w, ci, geom.korder)
     res = {}
     for mode, thr in (("f32", 0.0), ("f16x2", 1.0)):
         use_plan(conv_f16x2_min_flop=thr)
