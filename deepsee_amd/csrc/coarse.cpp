@@ -121,13 +121,16 @@ int norm_forward(const dsee_norm_layer& nl, const uint8_t* labels, int lab_h, in
     DSEE_TRY(dsee_absmax(nl.w2a, (long)rows * kHidden * 9, b.amax_u, stream));
     if (has_t) DSEE_TRY(dsee_absmax(nl.table, (long)N * 9 * rows * 32, b.amax_u, stream));
   }
+  // (with a style table: the embedding columns once, the table's columns per image -- the front of the buffer sized for N copies;
+  // the fused kernel takes that layout as groups = -N)
   if (has_t)
-    DSEE_TRY(dsee_wino43_weights_table(nl.w2a, nl.table, reinterpret_cast<float*>(b.u2), N, rows, kHidden, 2, b.amax_u, stream));
+    DSEE_TRY(dsee_wino43_weights_table_shared(nl.w2a, nl.table, reinterpret_cast<float*>(b.u2), N, rows, kHidden, 2, b.amax_u,
+                                              stream));
   else if (!b.u_ready)
     DSEE_TRY(dsee_wino43_weights(nl.w2a, reinterpret_cast<float*>(b.u2), rows, kHidden, 0, 2, b.amax_u, stream));
   // gamma/beta GEMM + output transform + normalise + modulate + LeakyReLU: one kernel, M never reaches HBM
   return dsee_spade_fused_fwd(b.v2, b.u2, b.amax_cat, DSEE_WINO_V_BOUND, b.amax_u, nl.bias_packed, x, b.mean, b.invstd, b.out_h,
-                              b.out_scale, N, H, W, C, rows, ld, has_t ? N : 1, nl.add_one, slope, b.amax_h, b.amax_xhat, b.sign_mask,
+                              b.out_scale, N, H, W, C, rows, ld, has_t ? -N : 1, nl.add_one, slope, b.amax_h, b.amax_xhat, b.sign_mask,
                               stream);
 }
 

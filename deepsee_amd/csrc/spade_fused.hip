@@ -137,14 +137,17 @@ __global__ __launch_bounds__(512) void spade_fused_fwd_kernel(FusedArgs a) {
   const unsigned voffu_l = dslab ? 0xFFFFFFF0u : voffu, voffv_l = dslab ? 0xFFFFFFF0u : voffv;
   const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc((void*)uniform_ptr(a.U2), 0, (int)a.u_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)uniform_ptr(a.V2), 0, (int)a.v_bytes, 0x00020000);
-  const unsigned PU = (unsigned)(a.G * a.u_group_bytes), PV = (unsigned)(a.T * 64);       // per position
+  const unsigned PU = (unsigned)a.u_pos_bytes, PV = (unsigned)(a.T * 64);                 // per position
   const unsigned QU = (unsigned)(2 * a.u_slab_bytes), QV = (unsigned)(2 * a.v_slab_bytes);   // per piece
-  const unsigned base_u = (unsigned)((long)g * a.u_group_bytes + (long)rg * 4096), base_v = (unsigned)(t0 * 64);
+  // ... but the last U piece, which in the shared + per-image layout is the image's own (FusedArgs): scalar arithmetic only
+  const unsigned QUL = (unsigned)(a.u_last_off + (long)g * a.u_last_img);
+  const unsigned base_u = (unsigned)((long)g * a.u_img_bytes + (long)rg * 4096), base_v = (unsigned)(t0 * 64);
   // piece pc of position pos (ring slot group par = pos % RD): one U and one V instruction per wave
   auto dma_u = [&](int par, int pc, unsigned opos) {
     unsigned char* dst = smem + (par * NP + pc) * PIECE + wave * 1024;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsu, (__attribute__((address_space(3))) void*)dst, 16,
-                                             (HALF_LAST && pc == NP - 1) ? voffu_l : voffu, opos + pc * QU, 0, 0);
+                                             (HALF_LAST && pc == NP - 1) ? voffu_l : voffu,
+                                             opos + (pc == NP - 1 ? QUL : pc * QU), 0, 0);
   };
   auto dma_v = [&](int par, int pc, unsigned opos) {
     unsigned char* dst = smem + UREG + (par * NP + pc) * PIECE + wave * 1024;
@@ -699,14 +702,17 @@ __global__ __launch_bounds__(1024) void spade_fused_fwd16_kernel(FusedArgs a) {
   const unsigned voff_l = dslab ? 0xFFFFFFF0u : voff;
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (void*)uniform_ptr(dma_v ? a.V2 : a.U2), 0, (int)(dma_v ? a.v_bytes : a.u_bytes), 0x00020000);
-  const unsigned PP_ = dma_v ? (unsigned)(a.T * 64) : (unsigned)(a.G * a.u_group_bytes);   // per position
+  const unsigned PP_ = dma_v ? (unsigned)(a.T * 64) : (unsigned)a.u_pos_bytes;             // per position
   const unsigned QQ_ = 2 * slab_bytes;                                                      // per piece
-  const unsigned base_o = dma_v ? (unsigned)(t0 * 64) : (unsigned)((long)g * a.u_group_bytes + (long)rg * 4096);
+  // ... but the last U piece (the image's own in the shared + per-image layout, see FusedArgs)
+  const unsigned QQL_ = dma_v ? (NP - 1) * QQ_ : (unsigned)(a.u_last_off + (long)g * a.u_last_img);
+  const unsigned base_o = dma_v ? (unsigned)(t0 * 64) : (unsigned)((long)g * a.u_img_bytes + (long)rg * 4096);
   unsigned char* const dbase = smem + (dma_v ? UREG : 0) + dw * 1024;
   auto dma = [&](int par, int pc, unsigned opos) {
     unsigned char* dst = dbase + (par * NP + pc) * PIECE;
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)dst, 16,
-                                             (HALF_LAST && pc == NP - 1) ? voff_l : voff, opos + pc * QQ_, 0, 0);
+                                             (HALF_LAST && pc == NP - 1) ? voff_l : voff,
+                                             opos + (pc == NP - 1 ? QQL_ : pc * QQ_), 0, 0);
   };
 
   // ---- fragment addresses
@@ -1003,7 +1009,7 @@ extern "C" void dsee_fused_set_stamps(float* p) { g_fused_stamps = p; }
 /* The fused SPADE / SEAN normalisation forward (see the head of this file).  V2 = dsee_wino43_input_f16x2(cat, amax_cat,
  * v_bound), U2 = dsee_wino43_weights[_table](..., split = 2, amax_u); groups = images with per-image tables, else 1. */
 
-static int spade_fused_launch(bool packed, const void* V2, const void* U2, const float* amax_cat, float v_bound,
+static int spade_fused_launch(bool packed, bool shared_u, const void* V2, const void* U2, const float* amax_cat, float v_bound,
                               const float* amax_u, const float* bias_packed, const float* x, const float* mean,
                               const float* invstd, float* out_h, float* out_scale, int N, int H, int W, int C, int rows, int K,
                               int groups, int stat_groups, float add_one, float slope, float* amax_h, float* amax_xhat,
@@ -1012,6 +1018,9 @@ static int spade_fused_launch(bool packed, const void* V2, const void* U2, const
   DSEE_CHECK_ARG(rows == 2 * C && C % 32 == 0 && H % 4 == 0 && W % 4 == 0 && (K == 128 || K == 160));
   DSEE_CHECK_ARG(groups == 1 || groups == N);
   DSEE_CHECK_ARG(stat_groups == 1 || stat_groups == N);
+  // the shared + per-image U (dsee_wino43_weights_table_shared): two-term operands with per-image tables, whose 32 columns are
+  // then the last piece -- ca = K - 32 is a multiple of 32, so no piece straddles the boundary
+  DSEE_CHECK_ARG(!shared_u || (!packed && groups == N && (K - 32) % 32 == 0));
   const int tpi = (H / 4) * (W / 4);
   DSEE_CHECK_ARG(tpi % 64 == 0);
   const long T = (long)N * tpi;
@@ -1040,7 +1049,19 @@ static int spade_fused_launch(bool packed, const void* V2, const void* U2, const
   a.u_slab_bytes = (long)rows * 64;
   const int kslab = packed ? 32 : 16;          // k's per 64-byte-row slab of the operand images
   a.u_group_bytes = (long)(K / kslab) * rows * 64;
-  const long vb = a.v_slab_bytes * (K / kslab), ub = a.u_group_bytes * 36 * groups;
+  const int np = packed ? (K + 63) / 64 : K / 32;
+  if (shared_u) {
+    a.u_pos_bytes = (long)((K - 32) / 16 + 2 * groups) * a.u_slab_bytes;
+    a.u_img_bytes = 0;
+    a.u_last_off = (long)((K - 32) / 16) * a.u_slab_bytes;
+    a.u_last_img = 2 * a.u_slab_bytes;
+  } else {
+    a.u_pos_bytes = (long)groups * a.u_group_bytes;
+    a.u_img_bytes = a.u_group_bytes;
+    a.u_last_off = (long)(np - 1) * 2 * a.u_slab_bytes;
+    a.u_last_img = 0;
+  }
+  const long vb = a.v_slab_bytes * (K / kslab), ub = a.u_pos_bytes * 36;
   DSEE_CHECK_ARG(vb < 0xFFFFFFF0L && ub < 0xFFFFFFF0L);   // operand tensors are addressed through one buffer resource each
   a.v_bytes = (unsigned)vb;
   a.u_bytes = (unsigned)ub;
@@ -1057,7 +1078,6 @@ static int spade_fused_launch(bool packed, const void* V2, const void* U2, const
   a.stamps = g_fused_stamps;
   const long ntile = (T / 64) * (rows / 64);
   DSEE_CHECK_ARG(ntile < 0x7FFFFFFF);
-  const int np = packed ? (K + 63) / 64 : K / 32;
   const int rd = packed ? 3 : 2;               // ring depth in positions (see the kernel): the packed operands are half the bytes
   const size_t lds = (size_t)rd * np * 16384;  // ring of rd positions: rd * NP pieces of U and of V, 8 KB each
   // DSEE_FUSED_W16 = 1 / 0 selects the 16-wave / 8-wave form (default: DSEE_FUSED_W16_DEFAULT)
@@ -1107,8 +1127,10 @@ int dsee_spade_fused_fwd(const void* V2, const void* U2, const float* amax_cat, 
                          const float* bias_packed, const float* x, const float* mean, const float* invstd, float* out_h,
                          float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, float add_one,
                          float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask, hipStream_t st) {
-  return spade_fused_launch(false, V2, U2, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
-                            C, rows, K, groups, 1, add_one, slope, amax_h, amax_xhat, sign_mask, st);
+  // groups = -N: N per-image tables with U2 = dsee_wino43_weights_table_shared (embedding columns once, table columns per image)
+  const bool su = groups < 0;
+  return spade_fused_launch(false, su, V2, U2, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
+                            C, rows, K, su ? -groups : groups, 1, add_one, slope, amax_h, amax_xhat, sign_mask, st);
 }
 
 /* 16-bit storage mode: the same kernel on PACKED ONE-TERM operands -- V1 = dsee_wino43_input_f16p(cat) [K/32][36*T][32] fp16,
@@ -1117,7 +1139,7 @@ int dsee_spade_fused_fwd_f16p(const void* V1, const void* U1, const float* amax_
                               const float* bias_packed, const float* x, const float* mean, const float* invstd, float* out_h,
                               float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, float add_one,
                               float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask, hipStream_t st) {
-  return spade_fused_launch(true, V1, U1, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
+  return spade_fused_launch(true, false, V1, U1, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
                             C, rows, K, groups, 1, add_one, slope, amax_h, amax_xhat, sign_mask, st);
 }
 
@@ -1126,7 +1148,7 @@ int dsee_spade_fused_fwd_sg(const void* V2, const void* U2, const float* amax_ca
                             const float* bias_packed, const float* x, const float* mean, const float* invstd, float* out_h,
                             float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, int stat_groups,
                             float add_one, float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask, hipStream_t st) {
-  return spade_fused_launch(false, V2, U2, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
+  return spade_fused_launch(false, false, V2, U2, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
                             C, rows, K, groups, stat_groups, add_one, slope, amax_h, amax_xhat, sign_mask, st);
 }
 
@@ -1135,7 +1157,7 @@ int dsee_spade_fused_fwd_f16p_sg(const void* V1, const void* U1, const float* am
                                  float* out_h, float* out_scale, int N, int H, int W, int C, int rows, int K, int groups,
                                  int stat_groups, float add_one, float slope, float* amax_h, float* amax_xhat,
                                  uint32_t* sign_mask, hipStream_t st) {
-  return spade_fused_launch(true, V1, U1, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
+  return spade_fused_launch(true, false, V1, U1, amax_cat, v_bound, amax_u, bias_packed, x, mean, invstd, out_h, out_scale, N, H, W,
                             C, rows, K, groups, stat_groups, add_one, slope, amax_h, amax_xhat, sign_mask, st);
 }
 

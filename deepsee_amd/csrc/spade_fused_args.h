@@ -30,6 +30,12 @@ struct FusedArgs {
                              // pass needs of h (the LeakyReLU branch) in 1/32 of the bytes
   long T;                    // tiles of the whole batch
   long v_slab_bytes, u_slab_bytes, u_group_bytes;
+  // spade_fused.hip: where a workgroup of image g finds its U pieces (two slabs each) within a position of u_pos_bytes.  Piece p
+  // below the last at g u_img_bytes + p 2 u_slab_bytes, the last piece at u_last_off + g u_last_img.  Replicated layout
+  // [36*G][K/16][rows]: (G u_group_bytes, u_group_bytes, (NP - 1) 2 u_slab_bytes, 0); shared + per-image layout [36][ca/16 shared
+  // slabs | G x 2 table slabs][rows] (dsee_wino43_weights_table_shared; the last piece is the table's): ((ca/16 + 2 G) u_slab_bytes,
+  // 0, ca/16 u_slab_bytes, 2 u_slab_bytes)
+  long u_pos_bytes, u_img_bytes, u_last_off, u_last_img;
   unsigned v_bytes, u_bytes; // sizes of the two operand tensors (< 4 GB)
   int tpi, tw;               // tiles per image / per tile row
   int H, W, C, rows;

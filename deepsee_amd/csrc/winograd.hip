@@ -1191,16 +1191,25 @@ __device__ __forceinline__ void store_u8(float* __restrict__ U, int split, size_
   }
 }
 
+// SHARED: the embedding columns stored ONCE instead of once per image -- U is then ONE group per position, [36][rows][ca + 32 N]
+// in the same slab form, image n's 32 table columns at ca + 32 n (per position [ca/16 shared slabs][rows] 64-byte rows, then
+// [N][2 table slabs][rows]).  The replicated layout writes the same 36 rows ca 4 bytes N times (151 of 189 MB at N = 8, rows =
+// 1024, ca = 128).  Only the item -> (image, row, column) map and the column a value is stored at differ between the two forms:
+// the transform and the store are the same code, so every 16-byte word is the word the replicated layout holds.
+template <bool SHARED>
 __global__ __launch_bounds__(256) void wino43_weight_table8_kernel(const float* __restrict__ w2a, const float* __restrict__ table,
                                                                    float* __restrict__ U, int N, int rows, int ca, int Kpad,
                                                                    int split, const float* __restrict__ amax) {
-  const unsigned K8 = (unsigned)Kpad >> 3;
+  const unsigned K8 = (unsigned)Kpad >> 3;     // (SHARED: Kpad = ca + 32 N, the columns of the one group)
   const size_t per = (size_t)rows * Kpad;
-  const long total = (long)N * rows * K8;
+  const long total = (long)(SHARED ? 1 : N) * rows * K8;
   const float sc = split >= 2 ? dsee_pow2_scale(dsee_amax_read(amax)) : 1.f;
   for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const unsigned iu = (unsigned)i, rr = iu / K8, n = rr / (unsigned)rows;
-    const int k0 = (int)(iu - rr * K8) * 8, row = (int)(rr - n * (unsigned)rows);
+    const unsigned iu = (unsigned)i, rr = iu / K8;
+    const int ks = (int)(iu - rr * K8) * 8;    // column the 8 values are stored at
+    // image, and the column k0 of its [ca | 32] operand the values are the transform of
+    const unsigned n = SHARED ? (ks < ca ? 0u : (unsigned)(ks - ca) >> 5) : rr / (unsigned)rows;
+    const int k0 = SHARED ? (ks < ca ? ks : ca + ((ks - ca) & 31)) : ks, row = (int)(rr - (SHARED ? 0u : n * (unsigned)rows));
     float g[8][9];
     if (k0 < ca) {          // 8 shared embedding columns: 72 contiguous floats of w2a
       const f32x4* src = reinterpret_cast<const f32x4*>(w2a + ((size_t)row * ca + k0) * 9);
@@ -1227,7 +1236,9 @@ __global__ __launch_bounds__(256) void wino43_weight_table8_kernel(const float* 
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) g[j][tap] = 0.f;
     }
-    ggt8(g, [&](int xi, const float (&v)[8]) { store_u8(U, split, (size_t)xi * N + n, per, rows, Kpad, row, k0, sc, v); });
+    ggt8(g, [&](int xi, const float (&v)[8]) {
+      store_u8(U, split, SHARED ? (size_t)xi : (size_t)xi * N + n, per, rows, Kpad, row, ks, sc, v);
+    });
   }
 }
 
@@ -1716,11 +1727,28 @@ int dsee_wino43_weights_table(const float* w2a, const float* table, float* U, in
   DSEE_CHECK_ARG(table && U && (ca == 0 || w2a) && ca % 32 == 0 && rows % 128 == 0 && (split < 2 || amax_w));
   const int Kpad = dsee_conv_kpad(1, 1, ca + 32);
   if (split != 1 && Kpad % 8 == 0)
-    wino43_weight_table8_kernel<<<wgrid((long)N * rows * Kpad / 8), 256, 0, st>>>(w2a, table, U, N, rows, ca, Kpad, split,
-                                                                                  amax_w);
+    wino43_weight_table8_kernel<false><<<wgrid((long)N * rows * Kpad / 8), 256, 0, st>>>(w2a, table, U, N, rows, ca, Kpad,
+                                                                                         split, amax_w);
   else
     wino43_weight_table_kernel<<<wgrid((long)N * rows * Kpad), 256, 0, st>>>(w2a, table, U, N, rows, ca, Kpad, split,
                                                                              amax_w);
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+/* The same operand for split = 2 with the embedding columns stored once: U per position [ca/16][rows] shared 64-byte rows, then
+ * [N][2][rows] table rows (position stride (ca/16 + 2 N) rows 64 bytes) -- what dsee_spade_fused_fwd reads with groups = -N.
+ * rows % 64 == 0: the fused kernel's row groups */
+int dsee_wino43_weights_table_shared(const float* w2a, const float* table, float* U, int N, int rows, int ca, int split,
+                                     const float* amax_w, hipStream_t st) {
+  DSEE_CHECK_ARG(table && U && w2a && amax_w && N >= 1 && ca >= 32 && ca % 32 == 0 && rows >= 64 && rows % 64 == 0);
+  if (split != 2) {
+    dsee_set_error("dsee_wino43_weights_table_shared: split = %d (the shared layout exists for the two-term fp16 form only)", split);
+    return DSEE_EUNSUPPORTED;
+  }
+  const long Kv = ca + 32L * N;       // the columns of the one group per position
+  DSEE_CHECK_ARG(rows * Kv / 8 < (1L << 31));     // (32-bit item index and column in the kernel)
+  wino43_weight_table8_kernel<true><<<wgrid(rows * Kv / 8), 256, 0, st>>>(w2a, table, U, N, rows, ca, (int)Kv, 2, amax_w);
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;
 }

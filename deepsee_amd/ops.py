@@ -2040,12 +2040,18 @@ def _norm_cat(w_sh, b_sh, labels, shift, n, h, w, has_a, has_t, cat_ups):
     return cat, cat_amax, actv_low
 
 
-def _norm_u(w2a, table, nb, rows, ca, kp, split):
+def _norm_u(w2a, table, nb, rows, ca, kp, split, shared=False):
     """(U, amax) of the gamma/beta convolution for `nb` images: the shared weights w2a alone, or per image with the rows of
-    `table` (the style half over the one-hot channels) behind them"""
+    `table` (the style half over the one-hot channels) behind them.  `shared` (two-term form, what the fused forward reads under
+    plan.shared_u): the embedding columns once per position and only the table's 32 columns per image."""
     if table is None:
         return _wino_u(w2a, rows, ca, False, rows, kp, split)
     ua = weight_amax(w2a, table) if split >= 2 else None
+    if shared:
+        assert split == 2 and kp == ca + 32
+        u = _i16(36 * (ca // 16 + 2 * nb) * rows * 32)
+        L.call("wino43_weights_table_shared", w2a, table, u, nb, rows, ca, 2, ua)
+        return u, ua
     u = _i16(36 * nb * rows * kp * {1: 3, 2: 2, 3: 1, 4: 1}[split]) if split else new(36, nb, rows, kp)
     L.call("wino43_weights_table", w2a, table, u, nb, rows, ca, int(split), ua)
     return u, ua
@@ -2065,7 +2071,9 @@ def _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out,
     pk = P().half       # 16-bit storage mode: packed one-term operands, one MFMA product (dsee_spade_fused_fwd_f16p)
     v2 = WinoOperand(_i16(36 * t * ld * (1 if pk else 2)), ac, F16P if pk else F16X2)
     L.call("wino43_input_f16p" if pk else "wino43_input_f16x2", cat, v2.data, n, h, w, ld, ac, FUSED_V_BOUND)
-    u, ua = _norm_u(w2a, table, n, rows, ca, kp, 4 if pk else 2)
+    # SEAN norm on BatchNorm statistics: the U with its embedding columns stored once (the entry point takes it as groups = -n)
+    su = (P().shared_u and table is not None and not pk and not P().fused_w4 and sg == 1 and ca >= 32 and ca % 32 == 0)
+    u, ua = _norm_u(w2a, table, n, rows, ca, kp, 4 if pk else 2, su)
     if PROFILE is not None:
         global PROFILE_OPERAND_GB
         PROFILE_OPERAND_GB += (t // 64) * (rows // 64) * 36 * 2 * 64 * ld * 4.0 / 1e9
@@ -2081,7 +2089,8 @@ def _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out,
         _call_sg("spade_fused_fwd_f16p" if pk else ("spade_fused_fwd_w4" if (P().fused_w4 and sg == 1) else
                                                     "spade_fused_fwd"), sg,
                  (v2.data, u, ac, FUSED_V_BOUND, ua, b2.contiguous(), x, mean, invstd, out, scale, n,
-                  h, w, c, rows, ld, n if table is not None else 1), (float(add_one), LRELU_SLOPE, hm, xm, smask))
+                  h, w, c, rows, ld, (-n if su else n) if table is not None else 1),
+                 (float(add_one), LRELU_SLOPE, hm, xm, smask))
         tag_amax(out, hm)
     # the weight / table gradient reads the split V the kernel above consumed, or an fp32 V of its own as its Q operand
     keep = v2 if _norm_keeps_v(scale, nb, n, ld, rows) else None

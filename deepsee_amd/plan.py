@@ -87,6 +87,11 @@ class KernelPlan:
     # by what the L2 -> LDS path delivers to a 64 x 64 block, not by how the block issues it (profiles/r06_fused_w4*.txt).  Off by
     # default (the 8-wave kernel also serves the 16-bit storage mode); kept under the same tests.
     fused_w4: bool = False
+    # the fused forward of a SEAN norm reads a U whose 128 embedding columns -- the same weights for every image -- are stored once
+    # and only the 32 style-table columns per image (dsee_wino43_weights_table_shared: 57 instead of 189 MB written per norm at
+    # N = 8, rows = 1024; the same words, the same output bits).  False: N complete per-image copies.  BatchNorm statistics, two-term
+    # operands and the 8- / 16-wave kernel only: InstanceNorm norms, the 16-bit mode and fused_w4 keep the replicated layout
+    shared_u: bool = True
     # the fused forward also writes the LeakyReLU branch of h as a bit mask ([pixel][C/32] words) and the two passes of the norm
     # backward read it instead of h (False: they read h, 32x the bytes, for its sign)
     sign_mask: bool = True

@@ -323,7 +323,8 @@ int dsee_wino43_weights_table(const float* w2a, const float* table, float* U, in
  *        scaled by a power of two known before the transform runs (|B^T d B| <= 100 max|d|; v_bound >= 100)
  *   U2 = dsee_wino43_weights[_table](..., split = 2, amax_u)   [36*groups][K/16][rows][2][16] fp16
  *   h [, scale] = dsee_spade_fused_fwd(...)   K = 128 (SPADE / capped) or 160 (SEAN: 128 + 32 one-hot), rows = 2 C,
- *        C % 32 == 0, (H/4)*(W/4) % 64 == 0, groups = N (per-image style tables) or 1; out_scale may be NULL.
+ *        C % 32 == 0, (H/4)*(W/4) % 64 == 0, groups = N (per-image style tables), -N (the same with U2 in the shared +
+ *        per-image layout of dsee_wino43_weights_table_shared, below) or 1; out_scale may be NULL.
  *        amax_h (optional, 64-line form, zeroed by the caller): receives max |h| -- the bound the convolution that consumes h
  *        needs BEFORE its input transform runs (dsee_wino43_input_f16x2 + dsee_gemm_f16x2_pre); amax_xhat (optional, same
  *        form): receives max |xhat|, which with max |dh| bounds the gamma/beta gradient of the backward pass
@@ -340,6 +341,18 @@ int dsee_spade_fused_fwd(const void* V2, const void* U2, const float* amax_cat, 
                          float* out_scale, int N, int H, int W, int C, int rows, int K, int groups, float add_one,
                          float slope, float* amax_h, float* amax_xhat, uint32_t* sign_mask,
                          hipStream_t stream);
+/* The shared + per-image layout of a SEAN norm's U2.  The K = ca + 32 columns of its gamma/beta convolution are ca embedding
+ * columns, whose weights w2a are the same for every image, and 32 one-hot columns, whose weights come from the per-image style
+ * table: dsee_wino43_weights_table writes the embedding columns once per image (151 of 189 MB at N = 8, rows = 1024).  Here, in
+ * the same 64-byte rows ([slab of 16 columns][row][2 terms][16] fp16), every one of the 36 positions holds
+ *     [ca/16 shared slabs][rows]   stored once,   then   [N][2 table slabs][rows]   per image
+ * (position stride (ca/16 + 2 N) rows 64 bytes); same expressions, same scale from the same amax slot, so every stored word is
+ * the word the replicated layout holds.  split = 2 only (DSEE_EUNSUPPORTED otherwise; the one-term and bf16x3 forms keep the
+ * replicated layout), ca % 32 == 0, ca >= 32, rows % 64 == 0 (the row groups of the fused kernel).
+ * dsee_spade_fused_fwd reads this layout when called with groups = -N (K = ca + 32; BatchNorm statistics, two-term operands); the
+ * bits of every output are those of groups = N on the replicated layout. */
+int dsee_wino43_weights_table_shared(const float* w2a, const float* table, float* U, int N, int rows, int ca, int split,
+                                     const float* amax_w, hipStream_t stream);
 size_t dsee_wino43_wgrad_table_workspace(long T, int N, int ca, int rows);
 int dsee_wino43_wgrad_table(const float* V, const float* dM, float* workspace, size_t workspace_bytes, float* dw2a,
                             float* dtable, long T, int N, int ca, int rows, int L, int split, const float* amax_v,
