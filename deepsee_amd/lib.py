@@ -5,6 +5,7 @@ importing/using it raises.  PyTorch only supplies device memory (``tensor.data_p
 current HIP stream handle.
 """
 import ctypes as C
+import enum
 import os
 import re
 
@@ -14,6 +15,36 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DSEE_LIB") or os.path.join(_HERE, "libdeepsee_hip.so")  # DSEE_LIB: kernel experiments only
 
 ACT_NONE, ACT_LRELU, ACT_RELU, ACT_TANH, ACT_MASK = 0, 1, 2, 3, 4
+
+
+class GemmKind(enum.IntEnum):
+    """The arithmetic of Winograd-domain weights U and of the NT GEMM that reads them; the values are the `split` argument of
+    dsee_wino43_weights[_table | _batch].  FP32: the grouped implicit-GEMM kernel; BF16X3: three bf16 terms per element; F16X2_AF32:
+    two scaled fp16 terms, an fp32 A operand is split inside the GEMM kernel; F16_AF32: ONE fp16 term, fp32 A operand; F16_PACKED:
+    one-term operands written packed by their producers (both: 16-bit storage mode; packed is chosen per call, ops._u_kind)."""
+    FP32, BF16X3, F16X2_AF32, F16_AF32, F16_PACKED = range(5)
+    # int16 words per weight element | the weights are scaled by their maximum | the product is scaled fp16: it needs a scale slot |
+    # bench.py's name of the GEMM | algorithmic HBM bytes per element of A, of U and of the product
+    words, needs_amax, f16_product, timer, bytes = (property(lambda k, i=i: _GEMM_KINDS[k][i]) for i in range(5))
+
+    def gemm_bytes(self, t, k_s, r_s, groups, rows):
+        """algorithmic HBM bytes of a Winograd-domain GEMM of this kind: A [36][t][k_s] + U [groups][rows][k_s] + the product [36][t][r_s]"""
+        a, u, m = self.bytes
+        return a * 36 * t * k_s + u * groups * rows * k_s + m * 36 * t * r_s
+
+
+_GEMM_KINDS = ((2, False, False, "winograd_gemm_128x128(igemm,36 groups)", (4.0, 6.0, 4.0)),      # (timed without its byte model)
+               (3, False, False, "winograd_gemm_bf16x3", (4.0, 6.0, 4.0)),
+               (2, True, False, "winograd_gemm_f16x2", (4.0, 4.0, 4.0)),
+               (1, True, True, "winograd_gemm_f16_1term", (4.0, 2.0, 2.0)),
+               (1, True, True, "winograd_gemm_f16_1term_packed", (2.0, 2.0, 2.0)))
+
+
+class WgradMode(enum.IntEnum):
+    """How the Winograd-domain weight gradient reduces over the tiles (ops._wgrad_mode; the kernel code of dsee_wino43_wgrad where
+    no finer one applies): on the fp32 MFMA | bf16x3 on pre-split transposed operands | on fp32 or kept pre-split operands,
+    transposed and split inside the GEMM (256-row tiles)."""
+    FP32, BF16X3_T, AF32 = range(3)
 
 
 class ConvGeom(C.Structure):

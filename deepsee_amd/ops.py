@@ -15,6 +15,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import lib as L
+from .lib import GemmKind, WgradMode     # (the integer codes of the Winograd kernels' arithmetic, with what each implies)
 from .plan import KernelPlan, DEFAULT_PLAN, current as P   # P(): the active KernelPlan of this thread (deepsee_amd/plan.py)
 
 LRELU_SLOPE = 0.2
@@ -526,19 +527,23 @@ def _wino_ok(n, h, w, cin_s, cout_s, k, stride, pad, ups):
             and cin_s >= 128 and _wino_chunk(n, h, w, max(cin_s, cout_s)) is not None)
 
 
-def _split_ok(k_s, r_s):
-    return P().gemm_split and k_s % 32 == 0 and r_s % 128 == 0
-
-
-def _split_kind(k_s, r_s):
-    """0: fp32 GEMM operands; 1: bf16x3; 2: fp16x2 (fp32 A operand split inside the GEMM kernel); 3: one fp16 term.
-    (4 = packed one-term operands written by their producers, the 16-bit storage mode: chosen per call by _pk_ok.)"""
-    if not _split_ok(k_s, r_s):
-        return 0
+def _u_kind(k_s, r_s, x_pk=False, dm_form=None, f16_only=False):
+    """The GemmKind of the weights U of one NT GEMM (k_s reduction, r_s output channels): the plan's for the shape, or packed where the
+    A operand is -- a forward V whose layer takes the packed chain (`x_pk`: _pk_ok), an adjoint GEMM whose dM is packed (`dm_form`).
+    `f16_only`: the fused norm and the spectral-norm group's batch transform, which exist in the two-term and the packed form only."""
+    if f16_only:
+        return GemmKind.F16_PACKED if P().half else GemmKind.F16X2_AF32
+    if dm_form == F16P:
+        return GemmKind.F16_PACKED
+    if not (P().gemm_split and k_s % 32 == 0 and r_s % 128 == 0):
+        return GemmKind.FP32
     af32 = P().gemm_af32 and k_s * 4 * 256 < 0x7FFFFFFF
     if P().half and af32:
-        return 3
-    return 2 if (P().gemm_f16x2 and af32) else 1
+        return GemmKind.F16_PACKED if x_pk else GemmKind.F16_AF32
+    return GemmKind.F16X2_AF32 if (P().gemm_f16x2 and af32) else GemmKind.BF16X3
+
+
+_split_kind = _u_kind       # (k_s, r_s): the kind the plan gives a shape, never F16_PACKED
 
 
 def _i16(n):
@@ -601,36 +606,26 @@ def weight_amax(*tensors):
     return a
 
 
-def _wino_u(w, co, ci, transpose_flip, rows, kp, split):
-    """Winograd-domain weights U [36][rows][kp]: fp32 (split 0), bf16x3-split rows (1) or scaled fp16x2-split rows (2).
-    Returns (U, amax) with amax = the device scalar the fp16x2 scale was derived from (None otherwise)."""
-    pre = getattr(w, "dsee_u", None)
-    if pre is not None and (int(transpose_flip), int(split), rows, kp) in pre:
-        return pre[(int(transpose_flip), int(split), rows, kp)]       # transformed with its whole network (SNGroup.wino_weights)
+def _u_key(transpose_flip, kind, rows, kp):
+    return (int(transpose_flip), int(kind), rows, kp)     # key of a U in `dsee_u`: SNGroup.wino_weights writes it, _wino_u reads
+
+
+def _wino_u(w, co, ci, transpose_flip, rows, kp, kind):
+    """Winograd-domain weights U [36][rows][kp] of `kind` (a GemmKind or its integer): fp32, or kind.words int16 words per element.
+    Returns (U, amax) with amax = the device scalar the fp16 scale was derived from (None where the kind has none)."""
+    kind, key, pre = GemmKind(kind), _u_key(transpose_flip, kind, rows, kp), getattr(w, "dsee_u", None)
+    if pre is not None and key in pre:
+        return pre[key]       # transformed with its whole network (SNGroup.wino_weights)
     def build():
-        if split >= 2 and getattr(w, "dsee_frozen", False):
+        if kind.needs_amax and getattr(w, "dsee_frozen", False):
             amax = torch.zeros(AMAX_FLOATS, dtype=torch.float32, device=w.device)     # (kept with the cached U: not a pool slot)
             L.call("absmax", w, w.numel(), amax)
         else:
-            amax = weight_amax(w) if split >= 2 else None
-        u = _i16(36 * rows * kp * {1: 3, 2: 2, 3: 1, 4: 1}[split]) if split else new(36, rows, kp)
-        L.call("wino43_weights", w, u, co, ci, int(transpose_flip), int(split), amax)
+            amax = weight_amax(w) if kind.needs_amax else None
+        u = _i16(36 * rows * kp * kind.words) if kind else new(36, rows, kp)
+        L.call("wino43_weights", w, u, co, ci, int(transpose_flip), int(kind), amax)
         return u, amax
-    return _frozen_cache(w, ("u", int(transpose_flip), int(split), rows, kp), build)
-
-
-def _gemm_bytes(t, k_s, r_s, groups, rows, split):
-    """algorithmic HBM bytes of a Winograd-domain GEMM: A (fp32, or 6 B/element pre-split) + B + C (fp32)"""
-    if split == 4:
-        return 2.0 * 36 * t * k_s + 2.0 * groups * rows * k_s + 2.0 * 36 * t * r_s
-    if split == 3:
-        return 4.0 * 36 * t * k_s + 2.0 * groups * rows * k_s + 2.0 * 36 * t * r_s
-    return 4.0 * 36 * t * k_s + (4.0 if split == 2 else 6.0) * groups * rows * k_s + 4.0 * 36 * t * r_s
-
-
-def _gemm_name(split):
-    return {1: "winograd_gemm_bf16x3", 2: "winograd_gemm_f16x2", 3: "winograd_gemm_f16_1term",
-            4: "winograd_gemm_f16_1term_packed"}[split]
+    return _frozen_cache(w, ("u",) + key, build)
 
 
 FUSED_V_BOUND = 100.0       # |B^T d B| <= 100 max|d| for F(4x4,3x3): scale of a pre-split V from max |input|
@@ -679,54 +674,53 @@ def _pk_ok(xc, t_g, r_s, k_s):
             and t_g % 256 == 0 and r_s % 128 == 0 and k_s % 32 == 0)
 
 
-def _wino_vgemm(xc, nb, h, wd, k_s, u, r_s, rows, kp, per_image, split, keep=None, u_amax=None):
+def _wino_vgemm(xc, nb, h, wd, k_s, u, r_s, rows, kp, per_image, kind, keep=None, u_amax=None):
     """(M [36][t][r_s], mscale) = V(xc) x U: input transform of `nb` images + the 36 (x nb with per-image weights) GEMMs.
     mscale: None (M is fp32) or the device scalar that rescales the fp16 M of the half-precision mode.
     `keep` (a list) receives V as a WinoOperand where the weight gradient can read it as its Q operand."""
     tpi = (h // 4) * (wd // 4)
     t = nb * tpi
     groups, t_g = (36 * nb, tpi) if per_image else (36, t)
-    m = torch.empty(36, t, r_s, dtype=torch.float16, device="cuda") if split in (3, 4) else new(36, t, r_s)
-    ms = amax_slot() if split in (3, 4) else None
+    m = torch.empty(36, t, r_s, dtype=torch.float16, device="cuda") if kind.f16_product else new(36, t, r_s)
+    ms = amax_slot() if kind.f16_product else None
     shape, flops = (36 * t, r_s, k_s, t_g, rows), 2.0 * 36 * t * k_s * r_s
-    if split == 1 and not (P().gemm_af32 and k_s * 4 * 256 < 0x7FFFFFFF):
+    if kind == GemmKind.BF16X3 and not (P().gemm_af32 and k_s * 4 * 256 < 0x7FFFFFFF):
         v = _i16(36 * t * k_s * 3)
         L.call("wino43_input_split", xc, v, nb, h, wd, k_s)
-        # algorithmic HBM bytes: A3 (6 B/element) + B3 + C (fp32)
-        with _timed(_gemm_name(1), flops, 6.0 * 36 * t * k_s + 6.0 * groups * rows * k_s + 4.0 * 36 * t * r_s):
+        with _timed(kind.timer, flops, 6.0 * 36 * t * k_s + 6.0 * groups * rows * k_s + 4.0 * 36 * t * r_s):
             L.call("gemm_bf16x3", v, u, m, *shape, 0)
         return m, ms
-    if split == 4 or (split == 2 and _presplit_ok(xc, t, t_g, r_s, k_s, keep is not None)):
+    pk = kind == GemmKind.F16_PACKED
+    if pk or (kind == GemmKind.F16X2_AF32 and _presplit_ok(xc, t, t_g, r_s, k_s, keep is not None)):
         # the input's maximum is known (written by its producer): the transform writes V already split (two scaled fp16 terms per
         # element; ONE in the 16-bit storage mode) with the scale fixed by |B^T d B| <= 100 max|d|; the GEMM streams it as it is
-        pk = split == 4
         v = WinoOperand(_i16(36 * t * k_s * (1 if pk else 2)), xc.dsee_amax, F16P if pk else F16X2)
         L.call("wino43_input_f16p" if pk else "wino43_input_f16x2", xc, v.data, nb, h, wd, k_s, v.amax, FUSED_V_BOUND)
     else:
-        v = WinoOperand(new(36, t, k_s), amax_slot() if split in (2, 3) else None, FP32)     # (its maximum: the fp16 GEMMs' scale)
+        v = WinoOperand(new(36, t, k_s), amax_slot() if kind.needs_amax else None, FP32)     # (its maximum: the fp16 GEMMs' scale)
         L.call("wino43_input", xc, v.data, nb, h, wd, k_s, v.amax)
-    if not split:
+    if kind == GemmKind.FP32:
         g = L.ConvGeom(groups, t_g, 1, k_s, t_g, 1, r_s, 1, 1, 1, 0, 1, 0, 0, 1)
-        with _timed("winograd_gemm_128x128(igemm,36 groups)", flops):
+        with _timed(kind.timer, flops):
             L.call("conv2d_fwd_grouped", C.byref(g), v.data, u, rows * kp, m)
         return m, ms
-    with _timed(_gemm_name(split), flops, _gemm_bytes(t, k_s, r_s, groups, rows, split)):
-        _wino_gemm(v, FUSED_V_BOUND, u, u_amax, m, shape, split, ms)
+    with _timed(kind.timer, flops, kind.gemm_bytes(t, k_s, r_s, groups, rows)):
+        _wino_gemm(v, FUSED_V_BOUND, u, u_amax, m, shape, kind, ms)
     if keep is not None:
         keep.append(v)         # the weight gradient's Q operand as it is
     return m, ms
 
 
-def _wino_gemm(a, bound, u, u_amax, m, shape, split, ms):
+def _wino_gemm(a, bound, u, u_amax, m, shape, kind, ms):
     """m = a x u, `shape` = (M, N, K, rows per group, weight rows) of the grouped NT GEMM: the kernel by the form of operand
-    a (pre-split: scaled by `bound` x a.amax) and, for an fp32 a, by the `split` kind of u; `ms`: slot for an fp16 m's scale."""
+    a (pre-split: scaled by `bound` x a.amax) and, for an fp32 a, by the GemmKind of u; `ms`: slot for an fp16 m's scale."""
     if a.form == F16P:
         L.call(_gemm_pre("gemm_f16p_pre", shape[2], shape[1]), a.data, u, m, *shape, a.amax, bound, u_amax, ms)
     elif a.form == F16X2:
         L.call(_gemm_pre("gemm_f16x2_pre", shape[2], shape[1]), a.data, u, m, *shape, a.amax, bound, u_amax)
-    elif split == 3:
+    elif kind == GemmKind.F16_AF32:
         L.call("gemm_f16_af32", a.data, u, m, *shape, 0, a.amax, u_amax, 1, ms)
-    elif split == 2:
+    elif kind == GemmKind.F16X2_AF32:
         L.call("gemm_f16x2_af32", a.data, u, m, *shape, 0, a.amax, u_amax)
     else:
         L.call("gemm_bf16x3_af32", a.data, u, m, *shape, 0)
@@ -741,28 +735,24 @@ def _wino_conv(x, w, n, h, wd, cin_s, cout_s, transpose_flip, bias=None, res=Non
     co, ci = w.shape[0], w.shape[1]
     r_s, k_s = (cin_s, cout_s) if transpose_flip else (cout_s, cin_s)   # GEMM output / reduction channels
     rows, kp = L.wrows(r_s), L.kpad(1, 1, k_s)
-    split = _split_kind(k_s, r_s)
     nb = _wino_chunk(n, h, wd, max(r_s, k_s))
-    if split == 3 and nb == n and _pk_ok(x, n * (h // 4) * (wd // 4), r_s, k_s):
-        split = 4
-    u, ua = _wino_u(w, co, ci, transpose_flip, rows, kp, split)
+    kind = _u_kind(k_s, r_s, x_pk=nb == n and _pk_ok(x, n * (h // 4) * (wd // 4), r_s, k_s))
+    u, ua = _wino_u(w, co, ci, transpose_flip, rows, kp, kind)
     y = new(n, h, wd, r_s)
     for n0 in range(0, n, nb):
         xc = x if nb == n else x[n0:n0 + nb]
         if nb != n and carried_amax(x) is not None:
             tag_amax(xc, x.dsee_amax)           # (the maximum of the whole batch bounds every chunk)
-        m, ms = _wino_vgemm(xc, nb, h, wd, k_s, u, r_s, rows, kp, False, split, keep if nb == n else None, ua)
+        m, ms = _wino_vgemm(xc, nb, h, wd, k_s, u, r_s, rows, kp, False, kind, keep if nb == n else None, ua)
         nz = (None, 0, 0) if noise is None else (noise[0], noise[1].seed, noise[1].offset + n0 * h * wd * r_s // 4)
         rz = ((None, 0, 0) if res_noise is None else
               (res_noise[0], res_noise[1].seed, res_noise[1].offset + n0 * h * wd * r_s // 4))
-        if stats and P().producer_stats and nb == n and (ms is None or split == 4) and act != L.ACT_MASK and _stats_rows_ok(r_s):
+        if (stats and P().producer_stats and nb == n and (ms is None or kind == GemmKind.F16_PACKED) and act != L.ACT_MASK
+                and _stats_rows_ok(r_s)):
             rows = L.lib().dsee_stats_part_rows(C.c_long(nb * (h // 4) * (wd // 4) * (r_s // 4)))
             part = new(rows, 3, r_s)
-            if ms is None:
-                L.call("wino43_output_stats", m, bias, res, res_ld or r_s, y, nb, h, wd, r_s, act, LRELU_SLOPE, *nz, *rz, part)
-            else:
-                L.call("wino43_output_stats_f16", m, bias, res, res_ld or r_s, y, nb, h, wd, r_s, act, LRELU_SLOPE, *nz, *rz,
-                       ms, part)
+            L.call("wino43_output_stats" if ms is None else "wino43_output_stats_f16", m, bias, res, res_ld or r_s, y, nb, h, wd,
+                   r_s, act, LRELU_SLOPE, *nz, *rz, *(() if ms is None else (ms,)), part)
             y.dsee_stats_rows = (part, rows)
             continue
         L.call("wino43_output", m, bias, None if res is None else res[n0:n0 + nb], res_ld or r_s, y[n0:n0 + nb], nb, h, wd,
@@ -771,32 +761,28 @@ def _wino_conv(x, w, n, h, wd, cin_s, cout_s, transpose_flip, bias=None, res=Non
 
 
 def _wgrad_mode(cin_s, cout_s):
-    """0: fp32-MFMA reduction; 1: bf16x3 with pre-split transposed operands; 2: bf16x3 with fp32 operands transposed and
-    split inside the GEMM (256-row tiles: cout_s % 256 == 0, cin_s == 160 or % 128 == 0)."""
+    """The WgradMode of a layer: AF32 takes 256-row tiles (cout_s % 256 == 0, cin_s == 160 or % 128 == 0)."""
     if not (P().gemm_split and cout_s % 128 == 0 and cin_s % 32 == 0):
-        return 0
+        return WgradMode.FP32
     if P().gemm_af32 and cout_s % 256 == 0 and (cin_s == 160 or cin_s % 128 == 0) and max(cin_s, cout_s) * 64 < 0x7FFFFFFF:
-        return 2
-    return 1
+        return WgradMode.AF32
+    return WgradMode.BF16X3_T
 
 
 def _wgrad_split(mode):
-    """`split` argument of dsee_wino43_wgrad[_table] for a weight-gradient mode: 3 = fp16x2, 4 = plain bf16, both on
-    fp32 operands transposed in the kernel."""
-    if mode == 2 and P().half:
+    """Kernel code of dsee_wino43_wgrad[_table] for a mode on fp32 operands: its value, or in AF32 3 = fp16x2, 4 = one fp16 term."""
+    if mode == WgradMode.AF32 and P().half:
         return 4
-    return 3 if (mode == 2 and P().gemm_f16x2) else mode
+    return 3 if (mode == WgradMode.AF32 and P().gemm_f16x2) else int(mode)
 
 
 def _wgrad_name(mode):
-    if not mode:
-        return "winograd_wgrad_128x128(36 groups)"
-    return "winograd_wgrad_" + {4: "f16_1term", 3: "f16x2"}.get(_wgrad_split(mode), "bf16x3")
+    return "winograd_wgrad_" + {0: "128x128(36 groups)", 4: "f16_1term", 3: "f16x2"}.get(_wgrad_split(mode), "bf16x3")
 
 
 def _dout_sums_ok(n, nb, cout_s, mode):
     """The channel sums over dY (bias / noise-weight gradients) can ride in the A dY A^T transform (dsee_wino43_dout_sums)."""
-    return P().dout_sums and nb == n and mode != 1 and cout_s // 4 <= 256 and 256 % (cout_s // 4) == 0
+    return P().dout_sums and nb == n and mode != WgradMode.BF16X3_T and cout_s // 4 <= 256 and 256 % (cout_s // 4) == 0
 
 
 # Every dM holds f_i f_j (A dY A^T)[i][j], f = (1, 1/4, 1/4, 1/16, 1/16, 1) (include/deepsee_hip.h, "ROW FACTORS": the absolute row
@@ -805,14 +791,15 @@ def _dout_sums_ok(n, nb, cout_s, mode):
 DM_BOUND = 1.0
 
 
-# `split` argument of dsee_wino43_wgrad[_table] per (V form, dM form); None: the weight-gradient mode decides (_wgrad_split)
+# kernel code of dsee_wino43_wgrad[_table] per (V form, dM form); None: the weight-gradient mode decides (_wgrad_split)
 _WGRAD_CODES = {(FP32, FP32): None, (BF16X3_T, BF16X3_T): None, (F16X2, FP32): 5, (F16X2, F16X2): 6, (F16P, F16P): 7}
 
 
 def _wgrad_code(v, dm, mode):
-    """`split` argument of dsee_wino43_wgrad[_table] for the operand forms at hand; a pairing no kernel takes raises
-    (a packed one-term V needs a packed one-term dM: dsee_gemm_f16p_tn_pqpre)."""
-    if (v.form, dm.form) not in _WGRAD_CODES or (v.form == BF16X3_T) != (mode == 1):
+    """Kernel code 0..7 of dsee_wino43_wgrad[_table] for the operand forms at hand, the one place that produces it; a pairing no
+    kernel takes raises (a packed one-term V needs a packed one-term dM: dsee_gemm_f16p_tn_pqpre)."""
+    mode = WgradMode(mode)
+    if (v.form, dm.form) not in _WGRAD_CODES or (v.form == BF16X3_T) != (mode == WgradMode.BF16X3_T):
         raise ValueError("no weight-gradient kernel for V %s x dM %s in mode %d" % (v.form, dm.form, mode))
     return _WGRAD_CODES[(v.form, dm.form)] or _wgrad_split(mode)
 
@@ -851,11 +838,11 @@ def _wino_dout(gc, nb, h, wd, cout_s, form, sums=None):
 
 
 def _wino_wgrad_operands(xc, gc, nb, h, wd, cin_s, cout_s, mode, v=None, dm=None, sums=None, pre_dm=False):
-    """(V, dM) of one image chunk for the Winograd-domain weight gradient, as WinoOperands: transposed bf16x3 in mode 1;
+    """(V, dM) of one image chunk for the Winograd-domain weight gradient, as WinoOperands: transposed bf16x3 in mode BF16X3_T;
     else `v` may be the V the forward pass kept and `dm` the A dY A^T its producer already wrote.  `pre_dm`: dM may leave
     its transform in the form of a pre-split `v` (when dY carries its maximum).  `sums`: see _wino_dout."""
     t = nb * (h // 4) * (wd // 4)
-    if mode == 1:
+    if mode == WgradMode.BF16X3_T:
         vt, dmt = _i16(36 * t * cin_s * 3), _i16(36 * t * cout_s * 3)
         L.call("wino43_input_split_t", xc, vt, nb, h, wd, cin_s)
         L.call("wino43_dout_split_t", gc, dmt, nb, h, wd, cout_s)
@@ -873,25 +860,50 @@ def _wino_wgrad_operands(xc, gc, nb, h, wd, cin_s, cout_s, mode, v=None, dm=None
 
 def _adjoint_ok(k_s, r_s):
     """dV = dM x U^T on the fp32-A split GEMM: k_s = channels of dy (reduction), r_s = channels of dx."""
-    return P().adjoint_dgrad and P().gemm_af32 and _split_ok(k_s, r_s) and k_s * 4 * 256 < 0x7FFFFFFF
+    return P().adjoint_dgrad and P().gemm_af32 and _split_kind(k_s, r_s) != GemmKind.FP32 and k_s * 4 * 256 < 0x7FFFFFFF
+
+
+WinoBwd = namedtuple("WinoBwd", "nb mode t whole pk pre_dm u_t as_dm")
+
+
+def _wino_bwd(n, nb, h, w, cin_s, cout_s, dx_s, v_form, g_amax=False, norm_c=None):
+    """The backward decisions of a Winograd layer cin_s -> cout_s that runs `nb` of its n images per pass (0: it does not run), under
+    the active plan: no tensors, no launches.  `dx_s`: channels of the data gradient wanted from the weight gradient's dM (adjoint
+    form), 0: none; `v_form`: form of the V the forward kept; `g_amax`: the output gradient carries its maximum; `norm_c`: the layer
+    is the gamma/beta convolution (ld -> rows) of a norm over norm_c channels.  -> t: tiles per pass; whole: one pass in mode AF32,
+    which reads the kept V; pk: the packed one-term chain; pre_dm: dM may leave its transform in the form of a kept pre-split V; u_t:
+    GemmKind of the adjoint U^T, None: dx does not come from dM; as_dm: the norm backward writes the dM all its consumers read."""
+    t, mode, norm = nb * (h // 4) * (w // 4), _wgrad_mode(cin_s, cout_s), norm_c is not None
+    whole = mode == WgradMode.AF32 and nb == n
+    adjoint = bool(nb and dx_s and mode != WgradMode.BF16X3_T and _adjoint_ok(cout_s, dx_s))
+    served = adjoint or not dx_s      # (a norm without an embedding has no dx; with one, dx must come from dM)
+    # 16-bit storage mode: the forward kept a packed one-term V -> A dY A^T packed one-term too, when dY's maximum is known
+    pk = bool(not norm and v_form == F16P and P().presplit_dm and whole and g_amax and t % 256 == 0 and cout_s % 32 == 0
+              and (not adjoint or cin_s % 128 == 0))
+    # ... pre-split when the whole chain can take it: a kept split V for the TN weight gradient, the adjoint GEMM on 256 x 256 tiles
+    pre_dm = (bool(v_form in (F16X2, F16P) and mode == WgradMode.AF32 and served) if norm else
+              pk or bool(P().presplit_dm and whole and _split_kind(cout_s, cin_s) == GemmKind.F16X2_AF32 and t % 256 == 0
+                         and cout_s % 16 == 0 and (not adjoint or (cin_s % 256 == 0 and (36 * t // 256) * (cin_s // 256) >= 512))))
+    as_dm = bool(norm and P().fuse_dm and nb == n and mode != WgradMode.BF16X3_T and served and 256 % (norm_c // 4) == 0)
+    return WinoBwd(nb, mode, t, whole, pk, pre_dm, _u_kind(cout_s, dx_s, dm_form=F16P if pk else None) if adjoint else None, as_dm)
 
 
 def _wino_dgrad_from_dm(dm, u_t, nb, h, wd, k_s, r_s, rows, mask=None, mask_ld=0):
     """dx [nb,h,wd,r_s] of a 3x3 convolution from the WinoOperand dm (dM [36][t][k_s] = A dY A^T): one grouped GEMM with the
-    transposed forward weights u_t = (U^T [36][rows][k_s] split, amax) and the overlap-add of the patches B dV B^T."""
-    t = nb * (h // 4) * (wd // 4)
-    split = 4 if dm.form == F16P else _split_kind(k_s, r_s)          # (the kind u_t was built with)
-    dv = torch.empty(36, t, r_s, dtype=torch.float16, device="cuda") if split in (3, 4) else new(36, t, r_s)
-    dvs = amax_slot() if split in (3, 4) else None
-    with _timed(_gemm_name(split), 2.0 * 36 * t * k_s * r_s, _gemm_bytes(t, k_s, r_s, 36, rows, split)):
-        _wino_gemm(dm, DM_BOUND, *u_t, dv, (36 * t, r_s, k_s, t, rows), split, dvs)
+    transposed forward weights u_t = (U^T [36][rows][k_s], amax, the GemmKind it was built with) and the overlap-add of B dV B^T."""
+    t, (u, ua, kind) = nb * (h // 4) * (wd // 4), u_t
+    assert (kind == GemmKind.F16_PACKED) == (dm.form == F16P), (kind, dm.form)
+    dv = torch.empty(36, t, r_s, dtype=torch.float16, device="cuda") if kind.f16_product else new(36, t, r_s)
+    dvs = amax_slot() if kind.f16_product else None
+    with _timed(kind.timer, 2.0 * 36 * t * k_s * r_s, kind.gemm_bytes(t, k_s, r_s, 36, rows)):
+        _wino_gemm(dm, DM_BOUND, u, ua, dv, (36 * t, r_s, k_s, t, rows), kind, dvs)
     dx = new(nb, h, wd, r_s)
     # max |dx| rides along: dx is the gradient w.r.t. a norm's output (bound of that norm's gamma/beta gradient) or, in the masked
     # form, the embedding's gradient (the dout operand of mlp_shared's weight gradient)
     tag_amax(dx, amax_slot())
     if mask is None and dvs is None and P().presplit_dm:
         L.call("wino43_input_adjoint_amax", dv, dx, nb, h, wd, r_s, dx.dsee_amax)
-    elif mask is None and split == 4 and P().presplit_dm:
+    elif mask is None and kind == GemmKind.F16_PACKED and P().presplit_dm:
         L.call("wino43_input_adjoint_amax_f16", dv, dx, nb, h, wd, r_s, dvs, dx.dsee_amax)
     else:
         L.call("wino43_input_adjoint", dv, mask, mask_ld, dx, nb, h, wd, r_s, dvs, dx.dsee_amax)
@@ -902,28 +914,21 @@ def _wino_wgrad(x, g, n, h, wd, cin_s, cout_s, co, ci, v_fwd=None, w_for_dx=None
     """dw OIHW of conv3x3(x, w) given g = dL/dy, reduced over tiles in the Winograd domain.  `v_fwd`: the WinoOperand V of
     x kept by the forward pass (used when the weight gradient takes fp32 operands and runs in one pass).
     `w_for_dx` (the weight): also return dx, computed from the same dM in the adjoint form -> (dw, dx)."""
-    nb = _wino_chunk(n, h, wd, max(cin_s, cout_s))
-    t, mode = nb * (h // 4) * (wd // 4), _wgrad_mode(cin_s, cout_s)
+    with_dx = w_for_dx is not None
+    bwd = _wino_bwd(n, _wino_chunk(n, h, wd, max(cin_s, cout_s)), h, wd, cin_s, cout_s, cin_s if with_dx else 0,
+                    getattr(v_fwd, "form", None), carried_amax(g) is not None)
+    assert not with_dx or bwd.u_t is not None
+    (nb, mode, t), total = bwd[:3], None
     nbytes = L.lib().dsee_wino43_wgrad_workspace(C.c_long(t), cin_s, cout_s)
     ws = scratch(nbytes, "wgrad")
-    total, with_dx = None, w_for_dx is not None
-    assert not with_dx or (mode != 1 and _adjoint_ok(cout_s, cin_s))
-    # 16-bit storage mode: the forward kept a packed one-term V -> A dY A^T packed one-term too (wgrad split 7, adjoint GEMM on
-    # dsee_gemm_f16p_pre), when dY's maximum is known
-    pk = (v_fwd is not None and v_fwd.form == F16P and P().presplit_dm and mode == 2 and nb == n and carried_amax(g) is not None
-          and t % 256 == 0 and cout_s % 32 == 0 and (not with_dx or cin_s % 128 == 0))
     if with_dx:
         rows_t = L.wrows(cin_s)
-        u_t = _wino_u(w_for_dx, co, ci, 2, rows_t, L.kpad(1, 1, cout_s), 4 if pk else _split_kind(cout_s, cin_s))
+        u_t = (*_wino_u(w_for_dx, co, ci, 2, rows_t, L.kpad(1, 1, cout_s), bwd.u_t), bwd.u_t)
         dx = new(n, h, wd, cin_s) if nb != n else None
-    # A dY A^T pre-split when the whole chain can take it: split V kept by the forward (-> wgrad split 6), and the adjoint GEMM
-    # (if any) on the 256 x 256 pre-split-A kernel
-    pre_dm = pk or (P().presplit_dm and mode == 2 and nb == n and _split_kind(cout_s, cin_s) == 2 and t % 256 == 0
-                    and cout_s % 16 == 0 and (not with_dx or (cin_s % 256 == 0 and (36 * t // 256) * (cin_s // 256) >= 512)))
     for n0 in range(0, n, nb):
         gc = g if nb == n else g[n0:n0 + nb]
-        v, dm = _wino_wgrad_operands(x[n0:n0 + nb], gc, nb, h, wd, cin_s, cout_s, mode,
-                                     v_fwd if (mode == 2 and nb == n) else None, sums=sums, pre_dm=pre_dm)
+        v, dm = _wino_wgrad_operands(x[n0:n0 + nb], gc, nb, h, wd, cin_s, cout_s, mode, v_fwd if bwd.whole else None, sums=sums,
+                                     pre_dm=bwd.pre_dm)
         dw = new(co, ci, 3, 3)
         with _timed(_wgrad_name(mode), 2.0 * 36 * t * cin_s * cout_s):
             L.call("wino43_wgrad", v.data, dm.data, ws, nbytes, dw, t, cin_s, cout_s, co, ci, _wgrad_code(v, dm, mode), v.amax,
@@ -952,22 +957,22 @@ ConvSpec = namedtuple("ConvSpec", "stride pad ups act noise_eps res_noise_eps re
 
 def _conv_path(n, hi, wi, cin_s, cout_s, co, ci, kh, kw, stride, pad, ups, has_res, exact, need_dx, need_dw):
     """The ConvPath of a layer of this geometry under the active plan: no tensors, no launches.  What depends on run-time tensor
-    state (a carried maximum, a chunked batch, pre_dm / pk) is decided by the helpers that own it."""
+    state (a carried maximum, the form of the kept V: pre_dm / pk) is decided in the backward pass, by _wino_bwd."""
     geom = L.geom_fwd(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
     wino = _wino_ok(n, hi, wi, cin_s, cout_s, kh, stride, pad, ups)
     thin3 = (not P().thin_gemm and kh == 3 and stride == 1 and pad == 1 and ups == 0 and co <= 4 and cin_s % 256 == 0
              and cin_s <= 1024 and wi % 64 == 0 and not has_res)
     thin1 = (P().thin_gemm and kh == 1 and kw == 1 and ups == 0 and co <= 32 and ci == cin_s and not has_res
              and geom.Ho == hi and geom.Wo == wi and cin_s >= 128)
-    mode = _wgrad_mode(cin_s, cout_s)
     wino_w = wino and P().winograd_wgrad and need_dw
-    adjoint = wino_w and mode != 1 and _adjoint_ok(cout_s, cin_s)      # one A dY A^T of g serves both gradients
+    bwd = _wino_bwd(n, _wino_chunk(n, hi, wi, max(cin_s, cout_s)) if wino_w else 0, hi, wi, cin_s, cout_s, cin_s, None)
+    adjoint = bwd.u_t is not None      # one A dY A^T of g serves both gradients
     dgrad = (None if not need_dx else THIN1 if thin1 else ADJOINT if adjoint else WINO if wino
              else S2_PARITY if _s2_parity_ok(geom, kh, kw) else DIRECT_SUMPOOL if ups else DIRECT)
     wgrad = None if not need_dw else THIN1 if thin1 else THIN3 if thin3 else WINO if wino_w else DIRECT
-    keep_v = wino and not thin3 and P().keep_v and need_dw and mode == 2
+    keep_v = wino and not thin3 and P().keep_v and need_dw and bwd.mode == WgradMode.AF32
     g_amax = P().presplit_dm if wino else (_direct_split_on(exact) and P().conv_amax_out)
-    dout_sums = wino_w and _dout_sums_ok(n, _wino_chunk(n, hi, wi, max(cin_s, cout_s)), cout_s, mode)
+    dout_sums = wino_w and _dout_sums_ok(n, bwd.nb, cout_s, bwd.mode)
     return ConvPath(THIN3 if thin3 else WINO if wino else DIRECT, dgrad, wgrad, bool(keep_v), bool(g_amax), bool(dout_sums))
 
 
@@ -1355,23 +1360,22 @@ class SNGroup:
         w0 = self.layers[0].weight_orig
         co, ci = w0.shape[0], w0.shape[1]
         same = all(tuple(m.weight_orig.shape) == tuple(w0.shape) for m in self.layers) and tuple(w0.shape[2:]) == (3, 3)
-        if not (same and P().winograd and P().gemm_split and P().gemm_f16x2 and P().gemm_af32 and ci % 32 == 0 and co % 128 == 0
-                and ci % 128 == 0 and ci >= 128):
+        if not (same and P().winograd and P().gemm_split and P().gemm_f16x2 and P().gemm_af32 and co % 128 == 0 and ci % 128 == 0):
             return
         out, amax = self.last
         nl = len(self.layers)
         stride = self.slices[1][0] - self.slices[0][0] if nl > 1 else co * ci * 9
-        sp = 4 if P().half else 2              # 16-bit storage mode: packed one-term weights
+        kind = _u_kind(ci, co, f16_only=True)              # (16-bit storage mode: packed one-term weights)
         for flip in ((0, 2) if with_adjoint else (0,)):
             r_s, k_s = (ci, co) if flip else (co, ci)
             rows, kp = L.wrows(r_s), L.kpad(1, 1, k_s)
-            per = 36 * rows * kp * (1 if sp == 4 else 2)     # int16 elements per layer (one / two fp16 terms)
+            per = 36 * rows * kp * kind.words     # int16 elements per layer (one / two fp16 terms)
             u = _i16(nl * per)
             with torch.no_grad():
-                L.call("wino43_weights_batch", out, u, nl, stride, per // 2, co, ci, flip, sp, amax)
+                L.call("wino43_weights_batch", out, u, nl, stride, per // 2, co, ci, flip, int(kind), amax)
             for i, m in enumerate(self.layers):
                 d = getattr(m._pre, "dsee_u", None) or {}
-                d[(flip, sp, rows, kp)] = (u[i * per:(i + 1) * per], amax[i])
+                d[_u_key(flip, kind, rows, kp)] = (u[i * per:(i + 1) * per], amax[i])
                 m._pre.dsee_u = d
 
 
@@ -2040,26 +2044,26 @@ def _norm_cat(w_sh, b_sh, labels, shift, n, h, w, has_a, has_t, cat_ups):
     return cat, cat_amax, actv_low
 
 
-def _norm_u(w2a, table, nb, rows, ca, kp, split, shared=False):
+def _norm_u(w2a, table, nb, rows, ca, kp, kind, shared=False):
     """(U, amax) of the gamma/beta convolution for `nb` images: the shared weights w2a alone, or per image with the rows of
     `table` (the style half over the one-hot channels) behind them.  `shared` (two-term form, what the fused forward reads under
     plan.shared_u): the embedding columns once per position and only the table's 32 columns per image."""
     if table is None:
-        return _wino_u(w2a, rows, ca, False, rows, kp, split)
-    ua = weight_amax(w2a, table) if split >= 2 else None
+        return _wino_u(w2a, rows, ca, False, rows, kp, kind)
+    ua = weight_amax(w2a, table) if kind.needs_amax else None
     if shared:
-        assert split == 2 and kp == ca + 32
+        assert kind == GemmKind.F16X2_AF32 and kp == ca + 32
         u = _i16(36 * (ca // 16 + 2 * nb) * rows * 32)
-        L.call("wino43_weights_table_shared", w2a, table, u, nb, rows, ca, 2, ua)
+        L.call("wino43_weights_table_shared", w2a, table, u, nb, rows, ca, int(kind), ua)
         return u, ua
-    u = _i16(36 * nb * rows * kp * {1: 3, 2: 2, 3: 1, 4: 1}[split]) if split else new(36, nb, rows, kp)
-    L.call("wino43_weights_table", w2a, table, u, nb, rows, ca, int(split), ua)
+    u = _i16(36 * nb * rows * kp * kind.words) if kind else new(36, nb, rows, kp)
+    L.call("wino43_weights_table", w2a, table, u, nb, rows, ca, int(kind), ua)
     return u, ua
 
 
 def _norm_keeps_v(scale, nb, n, ld, rows):
     """The V of `cat` is the Q operand of the weight / table gradient: kept for a backward pass that takes it whole"""
-    return P().keep_v and scale is not None and nb == n and _wgrad_mode(ld, rows) == 2
+    return P().keep_v and scale is not None and nb == n and _wgrad_mode(ld, rows) == WgradMode.AF32
 
 
 def _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one, rows, nb):
@@ -2068,12 +2072,13 @@ def _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out,
     (n, h, w, c), ld, sg = x.shape, cat.shape[3], stat_groups(mean)
     kp, t = L.kpad(1, 1, ld), n * (h // 4) * (w // 4)
     ac = cat_amax if cat_amax is not None else tensor_amax(cat)
-    pk = P().half       # 16-bit storage mode: packed one-term operands, one MFMA product (dsee_spade_fused_fwd_f16p)
+    kind = _u_kind(ld, rows, f16_only=True)
+    pk = kind == GemmKind.F16_PACKED    # 16-bit storage mode: packed one-term operands, one MFMA product (dsee_spade_fused_fwd_f16p)
     v2 = WinoOperand(_i16(36 * t * ld * (1 if pk else 2)), ac, F16P if pk else F16X2)
     L.call("wino43_input_f16p" if pk else "wino43_input_f16x2", cat, v2.data, n, h, w, ld, ac, FUSED_V_BOUND)
     # SEAN norm on BatchNorm statistics: the U with its embedding columns stored once (the entry point takes it as groups = -n)
     su = (P().shared_u and table is not None and not pk and not P().fused_w4 and sg == 1 and ca >= 32 and ca % 32 == 0)
-    u, ua = _norm_u(w2a, table, n, rows, ca, kp, 4 if pk else 2, su)
+    u, ua = _norm_u(w2a, table, n, rows, ca, kp, kind, su)
     if PROFILE is not None:
         global PROFILE_OPERAND_GB
         PROFILE_OPERAND_GB += (t // 64) * (rows // 64) * 36 * 2 * 64 * ld * 4.0 / 1e9
@@ -2103,14 +2108,14 @@ def _norm_product_fused(cat, cat_amax, w2a, table, ca, b2, x, mean, invstd, out,
 def _norm_product_wino(cat, w2a, table, ca, b2, x, mean, invstd, out, scale, add_one, rows, nb):
     """The gamma/beta GEMM in the Winograd domain, chunk by chunk, then dsee_wino43_output_modulate.  Returns the kept V."""
     (n, h, w, c), ld, sg = x.shape, cat.shape[3], stat_groups(mean)
-    kp, b2c, split = L.kpad(1, 1, ld), b2.contiguous(), _split_kind(ld, rows)
+    kp, b2c, kind = L.kpad(1, 1, ld), b2.contiguous(), _split_kind(ld, rows)
     keep = [] if _norm_keeps_v(scale, nb, n, ld, rows) else None
     for n0 in range(0, n, nb):
-        u, ua = _norm_u(w2a, None if table is None else table[n0:n0 + nb], nb, rows, ca, kp, split)
-        m, ms = _wino_vgemm(cat[n0:n0 + nb], nb, h, w, ld, u, rows, rows, kp, table is not None, split, keep, ua)
+        u, ua = _norm_u(w2a, None if table is None else table[n0:n0 + nb], nb, rows, ca, kp, kind)
+        m, ms = _wino_vgemm(cat[n0:n0 + nb], nb, h, w, ld, u, rows, rows, kp, table is not None, kind, keep, ua)
         px = nb * h * w
         with _timed("spade_modulate_fused", 0.0,
-                    (2.0 if split == 3 else 4.0) * 36 * (px // 16) * rows + 4.0 * px * c * (3 if scale is not None else 2)):
+                    kind.bytes[2] * 36 * (px // 16) * rows + 4.0 * px * c * (3 if scale is not None else 2)):
             # (InstanceNorm: the statistics rows of this pass's images)
             mc, ic = (mean, invstd) if sg == 1 else (mean[n0:n0 + nb], invstd[n0:n0 + nb])
             _call_sg("wino43_output_modulate", 1 if sg == 1 else nb,
@@ -2131,17 +2136,16 @@ def _norm_product(cat, cat_amax, w2a, table, b2, x, mean, invstd, out, scale, ad
     return None, None, None, None
 
 
-def _norm_wino_wgrad(cat, dgb, dm_all, vcat, w_for_dx, nc, nb, has_a, has_t, rows):
+def _norm_wino_wgrad(cat, dgb, dm_all, vcat, w_for_dx, nc, bwd, has_a, has_t, rows):
     """(dw2a, dtable, dactv): weight gradient of the gamma/beta convolution in the Winograd domain -- groups (xi, image), shared
     columns summed over images into dw2a, one-hot columns per image into dtable -- from the gamma/beta gradient dgb or, where the
-    norm backward wrote it, its dM `dm_all`.  `w_for_dx` (w2a): also the embedding's data gradient dactv, from the same dM."""
+    norm backward wrote it, its dM `dm_all`.  `w_for_dx` (w2a, where the WinoBwd `bwd` has a u_t): also dactv, from the same dM."""
     n, h, w, ld = cat.shape
     dw2a = dactv = None
-    t, ca, mode, with_dx = nb * (h // 4) * (w // 4), (NHIDDEN if has_a else 0), _wgrad_mode(ld, rows), w_for_dx is not None
+    (nb, mode, t), ca, with_dx = bwd[:3], (NHIDDEN if has_a else 0), w_for_dx is not None
     if with_dx:
-        rows_t = L.wrows(NHIDDEN)
-        u_t = _wino_u(w_for_dx, rows, NHIDDEN, 2, rows_t, L.kpad(1, 1, rows),
-                      4 if (dm_all is not None and dm_all.form == F16P) else _split_kind(rows, NHIDDEN))
+        rows_t, kind = L.wrows(NHIDDEN), _u_kind(rows, NHIDDEN, dm_form=getattr(dm_all, "form", None))   # (packed where dM is)
+        u_t = (*_wino_u(w_for_dx, rows, NHIDDEN, 2, rows_t, L.kpad(1, 1, rows), kind), kind)
         dactv = new(n, h, w, NHIDDEN) if nb != n else None
     nbytes = (L.lib().dsee_wino43_wgrad_table_workspace(C.c_long(t), nb, ca, rows) if has_t else
               L.lib().dsee_wino43_wgrad_workspace(C.c_long(t), ld, rows))
@@ -2149,7 +2153,7 @@ def _norm_wino_wgrad(cat, dgb, dm_all, vcat, w_for_dx, nc, nb, has_a, has_t, row
     wsw = scratch(nbytes, "wgrad")
     for n0 in range(0, n, nb):
         v, dm = _wino_wgrad_operands(cat[n0:n0 + nb], None if dm_all is not None else dgb[n0:n0 + nb], nb, h, w, ld, rows,
-                                     mode, vcat if (mode == 2 and nb == n) else None, dm_all)
+                                     mode, vcat if bwd.whole else None, dm_all)
         dwc = new(rows, NHIDDEN, 3, 3) if has_a else None
         tail = (_wgrad_code(v, dm, mode), v.amax, dm.amax)
         with _timed(_wgrad_name(mode), 2.0 * 36 * t * ld * rows):
@@ -2270,21 +2274,14 @@ class SeanNormTable(torch.autograd.Function):
         geom, lab, rows, nb = ctx.geom, ctx.labels, ctx.rows, ctx.wino_nb
         (n, h, w, c), ld = x.shape, cat.shape[3]
         dw_sh = db_sh = dw2a = dtable = db2 = dactv = None
-        mode = _wgrad_mode(ld, rows)
         wino_w = bool(nb) and (ctx.has_t or ctx.needs_input_grad[SeanNormTable.W2A])
-        # the embedding's data gradient from the weight gradient's dM (adjoint form): no second transform of the
-        # 1024-channel gamma/beta gradient
-        fused_d = wino_w and ctx.has_a and mode != 1 and _adjoint_ok(rows, NHIDDEN)
-        # every consumer of the gamma/beta gradient reads dM: let the norm backward write it directly
-        as_dm = P().fuse_dm and wino_w and nb == n and mode != 1 and (fused_d or not ctx.has_a) and 256 % (c // 4) == 0
+        bwd = _wino_bwd(n, nb if wino_w else 0, h, w, ld, rows, NHIDDEN if ctx.has_a else 0, getattr(vcat, "form", None), norm_c=c)
+        fused_d = bwd.u_t is not None     # the embedding's data gradient from the weight gradient's dM: no second transform of dgb
         add = ctx.grad_sink.take() if ctx.grad_sink is not None else None
-        # (pre-split dM needs both of its consumers on the pre-split kernels: the TN weight gradient reads the kept V2, the
-        # adjoint GEMM takes 256-row tiles)
-        pre_ok = vcat is not None and vcat.form in (F16X2, F16P) and mode == 2 and (not ctx.has_a or fused_d)
-        dx, dgb, cs, dm_all = modulate_bwd(dh, out, x, scale, mean, invstd, rows, ctx.sync, as_dm, add,
-                                           ctx.xhat_amax if pre_ok else None, ctx.sign_mask)
+        dx, dgb, cs, dm_all = modulate_bwd(dh, out, x, scale, mean, invstd, rows, ctx.sync, bwd.as_dm, add,
+                                           ctx.xhat_amax if bwd.pre_dm else None, ctx.sign_mask)
         # (the weight gradient runs before the embedding block when that block takes its dactv, after it otherwise)
-        wino_args = (cat, dgb, dm_all, vcat, w2a if fused_d else None, lab.nc, nb, ctx.has_a, ctx.has_t, rows)
+        wino_args = (cat, dgb, dm_all, vcat, w2a if fused_d else None, lab.nc, bwd, ctx.has_a, ctx.has_t, rows)
         if fused_d:
             dw2a, dtable, dactv = _norm_wino_wgrad(*wino_args)
         if ctx.has_a:

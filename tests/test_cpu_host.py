@@ -947,3 +947,196 @@ def test_conv2d_hands_every_setting_to_the_node_in_one_spec(monkeypatch):
     calls.clear()
     ops.conv2d(x, w, b, res, stride=2, res_noise=(rnw, reps), res_sink=sink)
     assert calls == [("upnoise", res, rnw, reps, 0), ("conv", x, w, b, "up", None, None, ops.ConvSpec(stride=2))]
+
+
+def _old_split_kind(ops, k_s, r_s):
+    """ops._split_kind as it stood on integers: 0 fp32, 1 bf16x3, 2 fp16x2 with an fp32 A operand, 3 one fp16 term"""
+    P = ops.P
+    if not (P().gemm_split and k_s % 32 == 0 and r_s % 128 == 0):
+        return 0
+    af32 = P().gemm_af32 and k_s * 4 * 256 < 0x7FFFFFFF
+    if P().half and af32:
+        return 3
+    return 2 if (P().gemm_f16x2 and af32) else 1
+
+
+def test_wino_kinds_and_backward_decisions_match_the_expressions_they_replaced():
+    """ops._u_kind and ops._wino_bwd against the inline expressions they replaced, restated here as they stood: the 3 -> 4
+    promotion of _wino_conv; pk, pre_dm and the adjoint-U kind of _wino_wgrad; the `4 if dm.form == F16P else _split_kind(..)` of
+    _wino_dgrad_from_dm and _norm_wino_wgrad; `4 if half else 2` of the fused norm and the spectral-norm group; _norm_keeps_v;
+    fused_d, as_dm and pre_ok of SeanNormTable.backward.  Grid: every Winograd layer of STEP_CONVS + EXTRA_CONVS and the norm
+    shapes (ld 32, 128 and 160; c = 256, 512 and two that are no power of two) x the default plan and each switch those expressions
+    read flipped x both values of "x / g carries a maximum" x every kept-V form and none."""
+    from deepsee_amd import ops, plan as PL
+    from deepsee_amd.lib import GemmKind, WgradMode
+    P, NH = ops.P, ops.NHIDDEN
+    assert [int(k) for k in GemmKind] == [0, 1, 2, 3, 4] and [int(m) for m in WgradMode] == [0, 1, 2]
+    assert ops.GemmKind is GemmKind and ops.WgradMode is WgradMode and ops._split_kind is ops._u_kind
+
+    def old_adjoint_ok(k_s, r_s):
+        return bool(P().adjoint_dgrad and P().gemm_af32 and (P().gemm_split and k_s % 32 == 0 and r_s % 128 == 0)
+                    and k_s * 4 * 256 < 0x7FFFFFFF)
+
+    def old_wino_wgrad(n, h, wd, cin_s, cout_s, want_dx, g_amax, v_form):
+        nb = ops._wino_chunk(n, h, wd, max(cin_s, cout_s))
+        t, mode = nb * (h // 4) * (wd // 4), ops._wgrad_mode(cin_s, cout_s)
+        with_dx = bool(want_dx and mode != 1 and old_adjoint_ok(cout_s, cin_s))      # (_conv_path's `adjoint`: the caller's promise)
+        pk = (v_form is not None and v_form == ops.F16P and P().presplit_dm and mode == 2 and nb == n and g_amax
+              and t % 256 == 0 and cout_s % 32 == 0 and (not with_dx or cin_s % 128 == 0))
+        u_t = (4 if pk else _old_split_kind(ops, cout_s, cin_s)) if with_dx else None
+        pre_dm = pk or (P().presplit_dm and mode == 2 and nb == n and _old_split_kind(ops, cout_s, cin_s) == 2 and t % 256 == 0
+                        and cout_s % 16 == 0 and (not with_dx or (cin_s % 256 == 0 and (36 * t // 256) * (cin_s // 256) >= 512)))
+        # the form dM then left _wino_wgrad_operands in
+        v = v_form if (mode == 2 and nb == n) else None
+        pre = bool(pre_dm and g_amax)
+        if v == ops.F16P and not pre:
+            v = None
+        dm_form = ops.BF16X3_T if mode == 1 else (v or ops.FP32) if pre else ops.FP32
+        return nb, t, mode, bool(pk), bool(pre_dm), u_t, dm_form
+
+    flips = ["gemm_split", "gemm_af32", "gemm_f16x2", "half", "half_norms", "presplit_a", "presplit_dm", "presplit_gb", "keep_v",
+             "adjoint_dgrad", "fuse_dm", "winograd_wgrad"]
+    plans = [PL.DEFAULT_PLAN] + [PL.DEFAULT_PLAN.replace(**{f: not getattr(PL.DEFAULT_PLAN, f)}) for f in flips]
+    plans.append(PL.DEFAULT_PLAN.replace(half=True, presplit_dm=False))
+    wino = sorted({s[:5] for s in STEP_CONVS + EXTRA_CONVS if ops._wino_ok(*s[:5], s[7], *s[9:12])})
+    assert len(wino) >= 10 and (8, 64, 64, 512, 512) in wino
+    # (n, h, w, c, has_a, has_t): SPADE (ld 128), SEAN (160) and PureSEAN (32) norms; rows = 2 c
+    norms = [(n, r, r, c, a, t) for n, r in ((2, 32), (2, 64), (8, 64)) for c in (256, 512, 384, 192)
+             for a, t in ((True, False), (True, True), (False, True))] + [(2, 30, 32, 256, True, True), (3, 64, 32, 256, True, False)]
+    forms = (None, ops.FP32, ops.F16X2, ops.F16P)
+    tagged, bare = torch.zeros(1), torch.zeros(1)
+    tagged.dsee_amax = torch.zeros(1)
+    seen = {"kind": set(), "mode": set(), "dm": set(), "flags": set(), "norm": set(), "u_t": set()}
+    for plan in plans:
+        with plan.active():
+            for f16_only_caller in ("fused norm", "spectral-norm group"):
+                assert ops._u_kind(160, 1024, f16_only=True) == (4 if P().half else 2)
+            for n, h, wd, cin_s, cout_s in wino:
+                if ops._wino_chunk(n, h, wd, max(cin_s, cout_s)) is None:
+                    continue
+                # forward, and the rotated-kernel data gradient (transpose_flip)
+                for r_s, k_s in ((cout_s, cin_s), (cin_s, cout_s)):
+                    assert ops._split_kind(k_s, r_s) == _old_split_kind(ops, k_s, r_s)
+                    for x in (tagged, bare):
+                        split, nb = _old_split_kind(ops, k_s, r_s), ops._wino_chunk(n, h, wd, max(r_s, k_s))
+                        if split == 3 and nb == n and ops._pk_ok(x, n * (h // 4) * (wd // 4), r_s, k_s):
+                            split = 4
+                        got = ops._u_kind(k_s, r_s, x_pk=nb == n and ops._pk_ok(x, n * (h // 4) * (wd // 4), r_s, k_s))
+                        assert isinstance(got, GemmKind) and got == split, (plan, n, h, wd, k_s, r_s)
+                        seen["kind"].add(got)
+                    for dm_form in (ops.FP32, ops.F16X2, ops.F16P, ops.BF16X3_T):
+                        assert ops._u_kind(k_s, r_s, dm_form=dm_form) == (4 if dm_form == ops.F16P else _old_split_kind(ops, k_s, r_s))
+                for want_dx in (False, True):
+                    for g_amax in (False, True):
+                        for v_form in forms:
+                            nb, t, mode, pk, pre_dm, u_t, dm_form = old_wino_wgrad(n, h, wd, cin_s, cout_s, want_dx, g_amax, v_form)
+                            got = ops._wino_bwd(n, nb, h, wd, cin_s, cout_s, cin_s if want_dx else 0, v_form, g_amax)
+                            assert isinstance(got, ops.WinoBwd) and isinstance(got.mode, WgradMode)
+                            assert got == (nb, mode, t, mode == 2 and nb == n, pk, pre_dm, u_t, False), (plan, n, h, wd, cin_s, cout_s)
+                            assert got.u_t is None or isinstance(got.u_t, GemmKind)
+                            seen["mode"].add(got.mode), seen["dm"].add(dm_form), seen["u_t"].add(got.u_t)
+                            seen["flags"].add((got.whole, got.pk, got.pre_dm, got.u_t is not None))
+            for n, h, wd, c, has_a, has_t in norms:
+                rows, ld = 2 * c, (NH if has_a else 0) + (32 if has_t else 0)
+                nb = ops._wino_mod_chunk(n, h, wd, c, rows, has_t)
+                mode = ops._wgrad_mode(ld, rows)
+                for scale in (None, tagged):
+                    assert bool(ops._norm_keeps_v(scale, nb, n, ld, rows)) == \
+                        bool(P().keep_v and scale is not None and nb == n and mode == 2)
+                for need_w2a in (False, True):
+                    for v_form in forms:
+                        wino_w = bool(nb) and (has_t or need_w2a)
+                        fused_d = wino_w and has_a and mode != 1 and old_adjoint_ok(rows, NH)
+                        as_dm = (P().fuse_dm and wino_w and nb == n and mode != 1 and (fused_d or not has_a)
+                                 and 256 % (c // 4) == 0)
+                        pre_ok = v_form is not None and v_form in (ops.F16X2, ops.F16P) and mode == 2 and (not has_a or fused_d)
+                        got = ops._wino_bwd(n, nb if wino_w else 0, h, wd, ld, rows, NH if has_a else 0, v_form, norm_c=c)
+                        assert (got.mode, got.u_t is not None, got.as_dm, got.pre_dm, got.pk) == \
+                            (mode, bool(fused_d), bool(as_dm), bool(pre_ok), False), (plan, n, h, wd, c, has_a, has_t, need_w2a, v_form)
+                        assert not wino_w or (got.nb, got.t, got.whole) == (nb, nb * (h // 4) * (wd // 4), mode == 2 and nb == n)
+                        for dm_form in (None, ops.FP32, ops.F16X2, ops.F16P):      # (what modulate_bwd / _wino_dout hand on)
+                            want = 4 if dm_form == ops.F16P else _old_split_kind(ops, rows, NH)
+                            assert ops._u_kind(rows, NH, dm_form=dm_form) == want
+                            assert not fused_d or dm_form == ops.F16P or got.u_t == want
+                            seen["kind"].add(ops._u_kind(rows, NH, dm_form=dm_form))
+                        seen["mode"].add(got.mode), seen["u_t"].add(got.u_t)
+                        seen["norm"].add((got.u_t is not None, got.as_dm, got.pre_dm))
+    assert ops.P() is PL.DEFAULT_PLAN
+    # the grid reaches every member of both enums, every dM form and both values of every flag
+    assert seen["kind"] == set(GemmKind) and seen["mode"] == set(WgradMode)
+    assert seen["u_t"] == {None} | set(GemmKind) - {GemmKind.FP32}         # (an adjoint GEMM always runs on split operands)
+    assert seen["dm"] == {ops.FP32, ops.F16X2, ops.F16P, ops.BF16X3_T}
+    assert all({f[i] for f in seen["flags"]} == {False, True} for i in range(4))
+    assert all({f[i] for f in seen["norm"]} == {False, True} for i in range(3))
+    with pytest.raises(AttributeError):
+        got.pk = True                                     # frozen
+
+
+def test_gemm_kind_tables_equal_the_literals_they_replaced():
+    """What a GemmKind carries -- int16 words per weight element, whether a weight maximum is needed, whether the product is scaled
+    fp16, the timer name, the byte model -- against the dictionary literals, the `>= 2` and `in (3, 4)` tests and the two ladders
+    (_gemm_name, _gemm_bytes) as they stood, for all five kinds; the callers that pass plain integers still can."""
+    from deepsee_amd import ops
+    from deepsee_amd.lib import GemmKind, WgradMode
+
+    def old_gemm_bytes(t, k_s, r_s, groups, rows, split):
+        if split == 4:
+            return 2.0 * 36 * t * k_s + 2.0 * groups * rows * k_s + 2.0 * 36 * t * r_s
+        if split == 3:
+            return 4.0 * 36 * t * k_s + 2.0 * groups * rows * k_s + 2.0 * 36 * t * r_s
+        return 4.0 * 36 * t * k_s + (4.0 if split == 2 else 6.0) * groups * rows * k_s + 4.0 * 36 * t * r_s
+
+    words = {1: 3, 2: 2, 3: 1, 4: 1}
+    names = {0: "winograd_gemm_128x128(igemm,36 groups)", 1: "winograd_gemm_bf16x3", 2: "winograd_gemm_f16x2",
+             3: "winograd_gemm_f16_1term", 4: "winograd_gemm_f16_1term_packed"}
+    for split in range(5):
+        kind = GemmKind(split)
+        assert kind == split and hash(kind) == hash(split) and "%d" % kind == str(split)
+        assert kind.words == words.get(split, 2)                 # (fp32 weights: 4 bytes; the literal had no entry, U is fp32 there)
+        assert kind.needs_amax is (split >= 2) and kind.f16_product is (split in (3, 4)) and kind.timer == names[split]
+        for t, k_s, r_s, groups, rows in ((512, 256, 256, 36, 256), (2048, 160, 1024, 36 * 8, 1024), (8192, 512, 512, 36, 512)):
+            assert kind.gemm_bytes(t, k_s, r_s, groups, rows) == old_gemm_bytes(t, k_s, r_s, groups, rows, split)
+        assert kind.bytes[2] == (2.0 if split in (3, 4) else 4.0)     # (the product's bytes, as _norm_product_wino modelled them)
+    # the functions tests and tools call with plain integers
+    assert ops._u_key(False, 2, 128, 160) == ops._u_key(0, GemmKind.F16X2_AF32, 128, 160) == (0, 2, 128, 160)
+    assert ops._dout_sums_ok(8, 8, 512, 2) and ops._dout_sums_ok(8, 8, 512, WgradMode.AF32) and not ops._dout_sums_ok(8, 8, 512, 1)
+    t = torch.zeros(1)
+    assert ops._wgrad_code(ops.WinoOperand(t, None, ops.FP32), ops.WinoOperand(t, None, ops.FP32), 0) == 0
+    assert type(ops._wgrad_code(ops.WinoOperand(t, None, ops.BF16X3_T), ops.WinoOperand(t, None, ops.BF16X3_T), 1)) is int
+    with pytest.raises(ValueError):
+        ops._wgrad_code(ops.WinoOperand(t, None, ops.FP32), ops.WinoOperand(t, None, ops.FP32), 3)       # no such mode
+    assert [ops._wgrad_name(m) for m in (0, 1)] == ["winograd_wgrad_128x128(36 groups)", "winograd_wgrad_bf16x3"]
+
+
+def test_u_cache_key_written_by_the_group_is_the_key_the_layer_looks_up(monkeypatch):
+    """SNGroup.wino_weights stores every layer's U under ops._u_key(..); ops._wino_u, asked for the kind the layer's forward
+    (flip 0) and its adjoint data gradient (flip 2) run with, finds it there and launches nothing -- in both precisions.  No
+    device: the launch and the allocation are replaced by recorders."""
+    from types import SimpleNamespace
+    from deepsee_amd import lib as L, ops, plan as PL
+    from deepsee_amd.options import make_opt
+    calls = []
+    monkeypatch.setattr(ops.L, "call", lambda name, *a: calls.append((name,) + a))
+    monkeypatch.setattr(ops, "_i16", lambda n: torch.empty(n, dtype=torch.int16))
+    co = ci = 256       # (weight-gradient mode AF32: the data gradient takes the adjoint form)
+    for plan, packed in ((PL.DEFAULT_PLAN, False), (PL.from_opt(make_opt(precision="fp16")), True)):
+        with plan.active():
+            layer = SimpleNamespace(weight_orig=torch.zeros(co, ci, 3, 3), _pre=torch.zeros(co, ci, 3, 3))
+            grp = ops.SNGroup([layer])
+            grp.slices, grp.last = [(0, co * ci * 9, 0, co, ci * 9)], (torch.zeros(co * ci * 9), torch.zeros(1, ops.AMAX_FLOATS))
+            calls.clear()
+            grp.wino_weights(with_adjoint=True)
+            assert [c[0] for c in calls] == ["wino43_weights_batch"] * 2
+            assert [c[9] for c in calls] == [4 if packed else 2] * 2 and all(type(c[9]) is int for c in calls)
+            rows, kp = L.wrows(co), L.kpad(1, 1, ci)
+            kind = ops.GemmKind.F16_PACKED if packed else ops.GemmKind.F16X2_AF32
+            assert set(layer._pre.dsee_u) == {ops._u_key(0, kind, rows, kp), ops._u_key(2, kind, rows, kp)}
+            calls.clear()
+            # the reader's side: the kinds _wino_conv and _wino_wgrad arrive at for this layer
+            fwd = ops._u_kind(ci, co, x_pk=packed)
+            adj = ops._wino_bwd(2, 2, 64, 64, ci, co, ci, ops.F16P if packed else ops.F16X2, g_amax=True).u_t
+            assert (fwd, adj) == (kind, kind)
+            for flip, k in ((0, fwd), (2, adj), (False, int(fwd))):
+                u, amax = ops._wino_u(layer._pre, co, ci, flip, rows, kp, k)
+                assert u is layer._pre.dsee_u[(int(flip), int(kind), rows, kp)][0] and amax.numel() == ops.AMAX_FLOATS
+            assert calls == []
