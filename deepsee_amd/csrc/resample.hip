@@ -1,6 +1,7 @@
 // Load-time geometry of the input pipeline on the device (deepsee_amd/resample.py builds the tables, deepsee_amd/data.py calls):
 //   dsee_resample_u8   Pillow's 8-bit separable resize (Image.resize with BICUBIC / BILINEAR / NEAREST on 'RGB' and 'L' images),
 //                      bit for bit, with the centre crop as a source box and the random crop as an output window
+//   dsee_resample_u8_ragged   the same two passes over a batch whose samples differ in source size: one arena + an item table
 //   dsee_interp_down   F.interpolate(hr, (S, S), mode = bilinear | nearest | area) + clamp(-1, 1)  (data/preprocessor.py:29-33)
 //   dsee_resize_hw     F.interpolate(x, (OH, OW), mode = bicubic | bilinear | nearest | area) [+ clamp(-1, 1)], down or up: the LR
 //                      image of a non-square batch (Preprocessor.downsample_image(hr, shape=(h, w))) and its bicubic 'baseline'
@@ -78,6 +79,82 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* __restri
   }
 }
 
+// ---- the ragged form: every sample has a source of its own inside one arena of src_bytes bytes, described by a row of `items`
+// (byte offset of the box's first pixel, row stride in bytes, box_w, box_h).  The two passes and their arithmetic are those above.
+
+// One output pixel of either pass: `cnt` taps over pixels `step` bytes apart, from the coefficients k[0 .. cnt - 1]
+template <int C>
+__device__ __forceinline__ void rs_taps(const uint8_t* __restrict__ p, long step, const int32_t* __restrict__ k, int cnt,
+                                        uint8_t* __restrict__ out) {
+  int acc[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) acc[c] = 1 << (RS_BITS - 1);
+  for (int t = 0; t < cnt; ++t) {
+    const int kk = k[t];
+#pragma unroll
+    for (int c = 0; c < C; ++c) acc[c] += (int)p[t * step + c] * kk;
+  }
+#pragma unroll
+  for (int c = 0; c < C; ++c) out[c] = rs_clip8(acc[c]);
+}
+
+struct rs_item {
+  long off, stride;
+  int bw, bh;
+};
+
+// Sample n's item row; false (the sample is skipped by both passes) unless its whole box lies inside the arena.  The bounds on
+// box_h and the stride keep (box_h - 1) * stride inside a long.
+template <int C>
+__device__ __forceinline__ bool rs_item_load(const int64_t* __restrict__ items, int n, long src_bytes, rs_item& it) {
+  const long off = items[4 * n], stride = items[4 * n + 1], bw = items[4 * n + 2], bh = items[4 * n + 3];
+  if (off < 0 || bw <= 0 || bh <= 0 || bw > (1L << 24) || bh > (1L << 24) || stride < bw * C || stride > (1L << 38)) return false;
+  if (bw * C > src_bytes || off > src_bytes - bw * C || (bh - 1) * stride > src_bytes - bw * C - off) return false;
+  it.off = off, it.stride = stride, it.bw = (int)bw, it.bh = (int)bh;
+  return true;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void resample_h_ragged_kernel(const uint8_t* __restrict__ src, long src_bytes,
+                                                                const int64_t* __restrict__ items, uint8_t* __restrict__ tmp, int N,
+                                                                int Wo, int tmp_rows, const int32_t* __restrict__ xtab, int kx,
+                                                                const int32_t* __restrict__ rows) {
+  const long total = (long)N * tmp_rows * Wo;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % Wo);
+    const long t = i / Wo;
+    const int r = (int)(t % tmp_rows), n = (int)(t / tmp_rows);
+    rs_item it;
+    if (!rs_item_load<C>(items, n, src_bytes, it)) continue;
+    const int sr = rows[2 * n] + r;
+    if (r >= rows[2 * n + 1] || sr < 0 || sr >= it.bh) continue;
+    const int32_t* tab = xtab + ((long)n * Wo + xo) * (2 + kx);
+    const int first = min(max(tab[0], 0), it.bw);
+    const int cnt = min(min(tab[1], kx), it.bw - first);
+    rs_taps<C>(src + it.off + (long)sr * it.stride + (long)first * C, C, tab + 2, cnt, tmp + i * C);
+  }
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void resample_v_ragged_kernel(const uint8_t* __restrict__ tmp, uint8_t* __restrict__ dst,
+                                                                long src_bytes, const int64_t* __restrict__ items, int N, int Wo,
+                                                                int Ho, int tmp_rows, const int32_t* __restrict__ ytab, int ky,
+                                                                const int32_t* __restrict__ rows) {
+  const long total = (long)N * Ho * Wo;
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int xo = (int)(i % Wo);
+    const long t = i / Wo;
+    const int yo = (int)(t % Ho), n = (int)(t / Ho);
+    rs_item it;
+    if (!rs_item_load<C>(items, n, src_bytes, it)) continue;
+    const int32_t* tab = ytab + ((long)n * Ho + yo) * (2 + ky);
+    const int avail = min(rows[2 * n + 1], tmp_rows);
+    const int first = min(max(tab[0], 0), max(avail, 0));
+    const int cnt = min(min(tab[1], ky), avail - first);
+    rs_taps<C>(tmp + (((long)n * tmp_rows + first) * Wo + xo) * C, (long)Wo * C, tab + 2, cnt, dst + i * C);
+  }
+}
+
 // NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3 channels (the rest of cs_out zero); sh = (float)H / S, sw = (float)W / S from the
 // host (dsee_interp.h: dsee_interp_px)
 __global__ __launch_bounds__(256) void interp_down_kernel(const float* __restrict__ x, float* __restrict__ y, int N, int H, int W,
@@ -132,6 +209,23 @@ int dsee_resample_u8(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int N, int 
     resample_h_kernel<1><<<rgrid(nh), 256, 0, st>>>(src + src_off, tmp, N, src_n_stride, src_row_stride, box_w, box_h, Wo,
                                                     tmp_rows, xtab, kx, rows);
     resample_v_kernel<1><<<rgrid(nv), 256, 0, st>>>(tmp, dst, N, Wo, Ho, tmp_rows, ytab, ky, rows);
+  }
+  DSEE_LAUNCH_CHECK();
+  return DSEE_OK;
+}
+
+int dsee_resample_u8_ragged(const uint8_t* src, long src_bytes, const int64_t* items, uint8_t* tmp, uint8_t* dst, int N, int C,
+                            int Wo, int Ho, int tmp_rows, const int32_t* xtab, int kx, const int32_t* ytab, int ky,
+                            const int32_t* rows, hipStream_t st) {
+  DSEE_CHECK_ARG(src && items && tmp && dst && xtab && ytab && rows && (C == 1 || C == 3));
+  DSEE_CHECK_ARG(src_bytes > 0 && N > 0 && Wo > 0 && Ho > 0 && tmp_rows > 0 && kx > 0 && ky > 0);
+  const long nh = (long)N * tmp_rows * Wo, nv = (long)N * Ho * Wo;
+  if (C == 3) {
+    resample_h_ragged_kernel<3><<<rgrid(nh), 256, 0, st>>>(src, src_bytes, items, tmp, N, Wo, tmp_rows, xtab, kx, rows);
+    resample_v_ragged_kernel<3><<<rgrid(nv), 256, 0, st>>>(tmp, dst, src_bytes, items, N, Wo, Ho, tmp_rows, ytab, ky, rows);
+  } else {
+    resample_h_ragged_kernel<1><<<rgrid(nh), 256, 0, st>>>(src, src_bytes, items, tmp, N, Wo, tmp_rows, xtab, kx, rows);
+    resample_v_ragged_kernel<1><<<rgrid(nv), 256, 0, st>>>(tmp, dst, src_bytes, items, N, Wo, Ho, tmp_rows, ytab, ky, rows);
   }
   DSEE_LAUNCH_CHECK();
   return DSEE_OK;

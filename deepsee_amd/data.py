@@ -18,6 +18,9 @@ and yields {'image_raw': uint8 [Hs,Ws,3], 'label_raw': uint8 [Hl,Wl], 'crop_pos'
 are uploaded as they are and dsee_resample_u8 does the centre crop, the resize (Pillow's 8-bit arithmetic, bit for bit) and the
 random crop on the device, which gives the wire format above.  The tables that drive it come from deepsee_amd/resample.py.
 DeviceLoader(workers=k) decodes the samples of a batch on k threads (PIL releases the GIL while it decodes).
+Files of different sizes in one batch (a user's own folder): DeviceLoader.collate packs them into one pinned arena (RawArena),
+which travels in one upload and goes through dsee_resample_u8_ragged, the same arithmetic with the source described per sample;
+all that is asked is that the samples leave the geometry with one size.
 
 Guided variant (opt.guiding_style_image): FolderDataset and RawFolderDataset add a second file of the same identity to every
 item ('guiding_label' / 'guiding_image', resp. 'guiding_label_raw' / 'guiding_image_raw' + 'guiding_path'), chosen through an
@@ -303,6 +306,31 @@ def stack_raw(arrays, paths=None):
     return torch.from_numpy(np.stack([np.asarray(a, dtype=np.uint8) for a in arrays]))
 
 
+class RawArena:
+    """Raw items of DIFFERENT sizes, as DeviceLoader.collate hands them on: `buf`, one uint8 buffer that holds the files back to
+    back, each from a 256-byte boundary (resample.pack_arena), and per item of this key its byte `offsets`, array `shapes`
+    ((h, w, 3) or (h, w)) and `paths`.  The samples and the guides of a kind share one buffer (the guides' items after the
+    samples'): one upload and one dsee_resample_u8_ragged call serve both."""
+
+    def __init__(self, buf, offsets, shapes, paths):
+        self.buf, self.offsets, self.shapes, self.paths = buf, list(offsets), [tuple(s) for s in shapes], list(paths)
+
+    def __len__(self):
+        return len(self.offsets)
+
+
+def _upload_tables(tab, keys):
+    """The integer tables `keys` of a table dict in one flat host-to-device transfer (int64 'items' travel as int32 pairs, first,
+    so that they stay 8-byte aligned) -> the dict of device views + 'tmp_rows'."""
+    flat = torch.from_numpy(np.concatenate([tab[k].reshape(-1).view(np.int32) for k in keys])).cuda(non_blocking=True)
+    dev, at = {"tmp_rows": tab["tmp_rows"]}, 0
+    for k in keys:
+        words = tab[k].size * tab[k].itemsize // 4
+        dev[k] = flat[at:at + words].view(torch.int64 if tab[k].itemsize == 8 else torch.int32).view(tab[k].shape)
+        at += words
+    return dev
+
+
 def resample_raw(opt, raw, crop_pos, filt, mode=None):
     """Load-time geometry of a raw uint8 batch [N,Hs,Ws(,3)] on the device: centre crop, resize and crop of opt.preprocess_mode
     (resample.load_geometry; `mode` instead, where given) through dsee_resample_u8 with `filt` -> uint8 [N,H,W(,3)], the wire
@@ -311,13 +339,46 @@ def resample_raw(opt, raw, crop_pos, filt, mode=None):
     n, hs, ws = raw.shape[:3]
     assert len(crop_pos) == n, "one crop position per sample"
     geos = [R.load_geometry(opt, (ws, hs), tuple(int(v) for v in p), mode) for p in crop_pos]
-    tab = R.batch_tables(geos, filt)
-    flat = torch.from_numpy(np.concatenate([tab[k].reshape(-1) for k in ("xtab", "ytab", "rows")])).cuda(non_blocking=True)
-    dev, at = {"tmp_rows": tab["tmp_rows"]}, 0
-    for k in ("xtab", "ytab", "rows"):
-        dev[k] = flat[at:at + tab[k].size].view(tab[k].shape)
-        at += tab[k].size
+    dev = _upload_tables(R.batch_tables(geos, filt), ("xtab", "ytab", "rows"))
     return ops.resample_u8(raw, dev, geos[0]["out"], geos[0]["box"])
+
+
+def resample_ragged(opt, parts, crop_pos, filt, mode=None, uploaded=None):
+    """resample_raw for raw items of different sizes: `parts`, RawArenas over ONE buffer (the samples [, the guides]), with one
+    crop position per item, through one dsee_resample_u8_ragged call -> uint8 [items,H,W(,3)].  The tables are built, and a
+    batch whose items leave the geometry with different sizes is refused (resample.ragged_tables), before anything is uploaded.
+    uploaded: {id(host buffer): device buffer} of the arenas already on the device."""
+    buf = parts[0].buf
+    assert all(p.buf is buf for p in parts), "the RawArenas of one call share one buffer"
+    shapes = [s for p in parts for s in p.shapes]
+    offsets, paths = [o for p in parts for o in p.offsets], [q for p in parts for q in p.paths]
+    assert len(crop_pos) == len(shapes), "one crop position per item"
+    c = {2: 1, 3: 3}[len(shapes[0])]
+    assert all(len(s) == len(shapes[0]) and (c == 1 or s[2] == 3) for s in shapes), "label maps [H,W] or RGB images [H,W,3]"
+    geos = [R.load_geometry(opt, (s[1], s[0]), tuple(int(v) for v in p), mode) for s, p in zip(shapes, crop_pos)]
+    tab = R.ragged_tables(geos, filt, [(s[1], s[0], c) for s in shapes], offsets, paths)
+    dev = _upload_tables(tab, ("items", "xtab", "ytab", "rows"))
+    uploaded = {} if uploaded is None else uploaded
+    if id(buf) not in uploaded:
+        uploaded[id(buf)] = buf if buf.is_cuda else buf.cuda(non_blocking=True)
+    return ops.resample_u8_ragged(uploaded[id(buf)], tab["items"], dev, geos[0]["out"], c)
+
+
+def collate_raw(arrays, paths, guides=None, guide_paths=None):
+    """The raw items of one kind (images or label maps) of a batch, host side -> (samples, guides or None).  Items of one size:
+    each a stacked uint8 tensor (stack_raw), as ever.  Samples or guides of different sizes: RawArenas over one buffer that holds
+    the samples' files, then the guides'."""
+    def uniform(items):
+        return items is None or all(a.shape == items[0].shape for a in items)
+
+    if uniform(arrays) and uniform(guides):
+        return stack_raw(arrays, paths), None if guides is None else stack_raw(guides, guide_paths)
+    n = len(arrays)
+    every = list(arrays) + list(guides or [])
+    buf, offsets = R.pack_arena(every)
+    shapes = [a.shape for a in every]
+    return (RawArena(buf, offsets[:n], shapes[:n], paths),
+            None if guides is None else RawArena(buf, offsets[n:], shapes[n:], guide_paths))
 
 
 def device_preprocess(opt, batch, stream=None):
@@ -328,7 +389,9 @@ def device_preprocess(opt, batch, stream=None):
     'bilinear' and BICUBIC otherwise (base_dataset.py:45-47), the label with NEAREST and the geometry of
     opt.label_preprocess_mode (None: opt.preprocess_mode, like the image).  'guiding_label_raw' / 'guiding_image_raw' share the
     samples' crop positions; where they also share their sizes, samples and guides go through dsee_resample_u8 as one batch of
-    2N (one call for the images, one for the label maps), otherwise through calls of their own."""
+    2N (one call for the images, one for the label maps), otherwise through calls of their own.  A raw key may also be a RawArena
+    (DeviceLoader.collate, collate_raw: items of different sizes); it goes through dsee_resample_u8_ragged, samples and guides of
+    a kind in one call of 2N items, and the batch is refused only if its items leave the geometry with different sizes."""
     def dev(t):
         return t if t.is_cuda else t.cuda(non_blocking=True)
 
@@ -336,8 +399,11 @@ def device_preprocess(opt, batch, stream=None):
         filt = R.BILINEAR if getattr(opt, "downsampling_method", "bicubic") == "bilinear" else R.BICUBIC
         lmode = getattr(opt, "label_preprocess_mode", None)        # celeba_dataset.py:53-55: 'resize' for the label maps
         wire, pos = dict(batch), list(batch["crop_pos"])
-        raws = {pre: (stack_raw(batch[pre + "image_raw"], batch.get(pre + "path", batch.get("path"))),
-                      stack_raw(batch[pre + "label_raw"], batch.get(pre + "path", batch.get("path"))))
+        def raw(key, paths):
+            return batch[key] if isinstance(batch[key], RawArena) else stack_raw(batch[key], paths)
+
+        raws = {pre: (raw(pre + "image_raw", batch.get(pre + "path", batch.get("path"))),
+                      raw(pre + "label_raw", batch.get(pre + "path", batch.get("path"))))
                 for pre in ("", "guiding_") if pre + "image_raw" in batch}
         n = len(pos)
 
@@ -347,7 +413,22 @@ def device_preprocess(opt, batch, stream=None):
             out[n:].copy_(b, non_blocking=True)
             return out
 
-        if len(raws) == 2 and all(raws[""][k].shape == raws["guiding_"][k].shape and raws[""][k].shape[0] == n for k in (0, 1)):
+        uploaded = {}
+
+        def kind(k, f, mode):                # images (k = 0) or label maps (1) of a batch in which some kind has mixed sizes
+            parts = [raws[pre][k] for pre in raws]
+            if any(isinstance(p, RawArena) for p in parts):     # (collate_raw: samples and guides are arenas together)
+                out = resample_ragged(opt, parts, pos * len(parts), f, mode, uploaded)
+            elif len(parts) == 2 and parts[0].shape == parts[1].shape and parts[0].shape[0] == n:
+                out = resample_raw(opt, both(*parts), pos * 2, f, mode)
+            else:
+                return [resample_raw(opt, p, pos, f, mode) for p in parts]
+            return [out[i * n:(i + 1) * n] for i in range(len(parts))]
+
+        if any(isinstance(v, RawArena) for pair in raws.values() for v in pair):
+            imgs, labs = kind(0, filt, None), kind(1, R.NEAREST, lmode)
+            done = {pre: (imgs[i], labs[i]) for i, pre in enumerate(raws)}
+        elif len(raws) == 2 and all(raws[""][k].shape == raws["guiding_"][k].shape and raws[""][k].shape[0] == n for k in (0, 1)):
             img = resample_raw(opt, both(raws[""][0], raws["guiding_"][0]), pos * 2, filt)
             lab = resample_raw(opt, both(raws[""][1], raws["guiding_"][1]), pos * 2, R.NEAREST, lmode)
             done = {"": (img[:n], lab[:n]), "guiding_": (img[n:], lab[n:])}
@@ -433,13 +514,15 @@ class DeviceLoader:
         if pin:
             out["flip"] = out["flip"].pin_memory()
         if "image_raw" in samples[0]:
-            keys = [("label_raw", "path"), ("image_raw", "path")]
-            if "guiding_image_raw" in samples[0]:
+            guided = "guiding_image_raw" in samples[0]
+            if guided:
                 out["guiding_path"] = [s.get("guiding_path", "") for s in samples]
-                keys += [("guiding_label_raw", "guiding_path"), ("guiding_image_raw", "guiding_path")]
-            for key, names in keys:
-                t = stack_raw([s[key] for s in samples], out[names])
-                out[key] = t.pin_memory() if pin else t
+            for key in ("label_raw", "image_raw"):     # one size: stacked and pinned; mixed sizes: the arena form (pinned by pack_arena)
+                t, g = collate_raw([s[key] for s in samples], out["path"],
+                                   [s["guiding_" + key] for s in samples] if guided else None, out.get("guiding_path"))
+                out[key] = t.pin_memory() if pin and isinstance(t, torch.Tensor) else t
+                if guided:
+                    out["guiding_" + key] = g.pin_memory() if pin and isinstance(g, torch.Tensor) else g
             out["crop_pos"] = [tuple(s["crop_pos"]) for s in samples]
             return out
         out["label"], out["image"] = stack("label"), stack("image")

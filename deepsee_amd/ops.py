@@ -12,6 +12,7 @@ import threading
 from collections import namedtuple
 from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import lib as L
@@ -276,6 +277,31 @@ def resample_u8(src, tables, out_wh, box=None):
     dst = torch.empty((n, ho, wo, c) if src.dim() == 4 else (n, ho, wo), dtype=torch.uint8, device="cuda")
     L.call("resample_u8", src, tmp, dst, n, c, (y0 * ws + x0) * c, hs * ws * c, ws * c, bw, bh, wo, ho, tmp_rows,
            xtab, xtab.shape[2] - 2, ytab, ytab.shape[2] - 2, rows)
+    return dst
+
+
+def resample_u8_ragged(arena, items_host, tables, out_wh, c):
+    """dsee_resample_u8_ragged: the sources of N samples of different sizes in one uint8 device arena (resample.pack_arena) through
+    the tables of resample.ragged_tables (on the device: 'xtab', 'ytab', 'rows' int32, 'items' int64 [N,4] + the int 'tmp_rows')
+    -> uint8 [N,Ho,Wo,3] for c = 3, [N,Ho,Wo] for c = 1.  items_host is the host copy of 'items': every sample's box is checked
+    against the arena here, before the call."""
+    items_host = np.asarray(items_host, dtype=np.int64)         # (numpy: a handful of N-element operations, microseconds)
+    n, size = items_host.shape[0], arena.numel()
+    assert arena.dtype == torch.uint8 and arena.dim() == 1 and arena.is_contiguous() and c in (1, 3)
+    assert items_host.shape == (n, 4)
+    off, stride, bw, bh = items_host.T
+    assert off.min() >= 0 and bw.min() > 0 and bh.min() > 0, "item table: negative offset or empty box"
+    assert (stride >= bw * c).all(), "item table: a row stride below box_w * c"
+    assert (off + (bh - 1) * stride + bw * c).max() <= size, "item table: a box reaches past the arena's %d bytes" % size
+    wo, ho = out_wh
+    xtab, ytab, rows, items, tmp_rows = tables["xtab"], tables["ytab"], tables["rows"], tables["items"], tables["tmp_rows"]
+    assert tuple(xtab.shape[:2]) == (n, wo) and tuple(ytab.shape[:2]) == (n, ho) and tuple(rows.shape) == (n, 2)
+    assert xtab.dtype == ytab.dtype == rows.dtype == torch.int32 and items.dtype == torch.int64 and tuple(items.shape) == (n, 4)
+    assert 0 < tmp_rows <= int(bh.max())
+    tmp = scratch(n * tmp_rows * wo * c, "resample").view(torch.uint8)
+    dst = torch.empty((n, ho, wo, c) if c == 3 else (n, ho, wo), dtype=torch.uint8, device="cuda")
+    L.call("resample_u8_ragged", arena, size, items, tmp, dst, n, c, wo, ho, tmp_rows, xtab, xtab.shape[2] - 2,
+           ytab, ytab.shape[2] - 2, rows)
     return dst
 
 

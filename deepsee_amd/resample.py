@@ -10,7 +10,8 @@ BICUBIC (a = -0.5, support 2) and BILINEAR (support 1); nearest_table restates t
 Geometry.  load_geometry returns {'box': (x, y, w, h) in the file, 'resize': (w, h) or None, 'window': (x, y, w, h) in the resized
 image, 'out': (w, h)} for every preprocess_mode of options/base_options.py:56-63; where PIL / torchvision would pad (a crop that
 leaves the image) it raises ValueError.  batch_tables cuts the tables down to each sample's window, in the layout of
-include/deepsee_hip.h.
+include/deepsee_hip.h.  ragged_tables does the same for files of different sizes (dsee_resample_u8_ragged): per-sample boxes, an
+item table that says where each sample's box lies in the arena pack_arena builds, and one output size asked of all.
 """
 import functools
 
@@ -181,21 +182,24 @@ def axis_tables(geo, filt):
     return tuple(t[x:x + w] for t in xt), tuple(t[y:y + h] for t in yt)
 
 
+def pack(ts, rebase=None):
+    """Per-sample tables of one axis -> int32 [N, out, 2 + k], k the largest tap count of the batch (shorter rows zero-padded; the
+    count column says how many are read); rebase[n] is subtracted from sample n's first indices."""
+    k = max(t[2].shape[1] for t in ts)
+    out = np.zeros((len(ts), len(ts[0][0]), 2 + k), np.int32)
+    for n, (first, count, coef) in enumerate(ts):
+        out[n, :, 0] = first - (rebase[n] if rebase is not None else 0)
+        out[n, :, 1] = count
+        out[n, :, 2:2 + coef.shape[1]] = coef
+    return out
+
+
 def batch_tables(geos, filt):
     """The int32 arguments of dsee_resample_u8 for a batch of geometries with one box size and one output size:
     {'xtab' [N, Wo, 2 + kx], 'ytab' [N, Ho, 2 + ky], 'rows' [N, 2], 'tmp_rows'} -- the ytab's first indices rebased to the
     first source row each sample reads."""
     tabs = [axis_tables(g, filt) for g in geos]
     bw, bh = geos[0]["box"][2:]
-
-    def pack(ts, rebase=None):
-        k = max(t[2].shape[1] for t in ts)
-        out = np.zeros((len(ts), len(ts[0][0]), 2 + k), np.int32)
-        for n, (first, count, coef) in enumerate(ts):
-            out[n, :, 0] = first - (rebase[n] if rebase is not None else 0)
-            out[n, :, 1] = count
-            out[n, :, 2:2 + coef.shape[1]] = coef
-        return out
 
     rows = np.array([[int(yt[0].min()), int((yt[0] + yt[1]).max() - yt[0].min())] for _, yt in tabs], np.int32)
     xtab, ytab = pack([t[0] for t in tabs]), pack([t[1] for t in tabs], rows[:, 0])
@@ -204,3 +208,56 @@ def batch_tables(geos, filt):
     assert ytab[..., 0].min() >= 0 and ((ytab[..., 0] + ytab[..., 1]).max(1) <= rows[:, 1]).all()
     assert rows[:, 0].min() >= 0 and (rows.sum(1) <= bh).all()
     return {"xtab": xtab, "ytab": ytab, "rows": rows, "tmp_rows": int(rows[:, 1].max())}
+
+
+ARENA_ALIGN = 256     # every file of an arena starts on a multiple of this many bytes
+
+
+def pack_arena(arrays):
+    """uint8 arrays of any shapes back to back in one uint8 buffer, each start ARENA_ALIGN-byte aligned -> (buffer, [byte offset
+    per array]).  The buffer is a torch tensor, pinned when CUDA is available: one upload carries the whole batch."""
+    import torch
+    arrays = [np.ascontiguousarray(a, dtype=np.uint8) for a in arrays]
+    offsets, at = [], 0
+    for a in arrays:
+        at = (at + ARENA_ALIGN - 1) // ARENA_ALIGN * ARENA_ALIGN
+        offsets.append(at)
+        at += a.size
+    buf = torch.empty(max(at, 1), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    view, end = buf.numpy(), 0
+    for a, off in zip(arrays, offsets):
+        view[end:off] = 0                                                       # (the padding is never read; kept defined)
+        view[off:off + a.size] = a.reshape(-1)
+        end = off + a.size
+    view[end:] = 0
+    return buf, offsets
+
+
+def ragged_tables(geos, filt, files, offsets, paths=None):
+    """batch_tables without its one-box assumption: the arguments of dsee_resample_u8_ragged for geometries whose boxes differ,
+    as long as all have one output size.  files: (w, h, channels) of every file, offsets: its first byte in the arena
+    (pack_arena).  {'xtab', 'ytab', 'rows', 'tmp_rows'} as in batch_tables -- kx, ky padded to the batch maximum, tmp_rows the
+    maximum row count -- plus 'items' int64 [N, 4]: (byte offset of the box's first pixel in the arena, row stride in bytes,
+    box_w, box_h).  Geometries that differ in their output size are refused (ValueError naming the first two that do)."""
+    names = list(paths) if paths is not None else list(range(len(geos)))
+    for n, g in enumerate(geos):
+        if g["out"] != geos[0]["out"]:
+            raise ValueError("the samples of one batch must leave the load-time geometry with one size: %s (%d x %d) becomes "
+                             "%d x %d, %s (%d x %d) becomes %d x %d"
+                             % ((names[0],) + tuple(files[0][:2]) + tuple(geos[0]["out"])
+                                + (names[n],) + tuple(files[n][:2]) + tuple(g["out"])))
+    tabs = [axis_tables(g, filt) for g in geos]
+
+    rows = np.array([[int(yt[0].min()), int((yt[0] + yt[1]).max() - yt[0].min())] for _, yt in tabs], np.int32)
+    xtab, ytab = pack([t[0] for t in tabs]), pack([t[1] for t in tabs], rows[:, 0])
+    items = np.zeros((len(geos), 4), np.int64)
+    for n, (g, (w, h, c), off) in enumerate(zip(geos, files, offsets)):
+        x0, y0, bw, bh = g["box"]
+        # what the kernel relies on, per sample: the box inside its file, every tap inside the box resp. inside the rows of the
+        # horizontal pass
+        assert 0 <= x0 and 0 <= y0 and x0 + bw <= w and y0 + bh <= h and c in (1, 3) and off >= 0, (g["box"], files[n], off)
+        assert xtab[n, :, 0].min() >= 0 and (xtab[n, :, 0] + xtab[n, :, 1]).max() <= bw and xtab[n, :, 1].max() <= xtab.shape[2] - 2
+        assert ytab[n, :, 0].min() >= 0 and (ytab[n, :, 0] + ytab[n, :, 1]).max() <= rows[n, 1]
+        assert rows[n, 0] >= 0 and rows[n].sum() <= bh
+        items[n] = (int(off) + (y0 * w + x0) * c, w * c, bw, bh)
+    return {"xtab": xtab, "ytab": ytab, "rows": rows, "tmp_rows": int(rows[:, 1].max()), "items": items}

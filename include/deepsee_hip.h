@@ -745,6 +745,18 @@ int dsee_label_u8_prepare(const uint8_t* lab, const uint8_t* flip, uint8_t* out,
 int dsee_resample_u8(const uint8_t* src, uint8_t* tmp, uint8_t* dst, int N, int C, long src_off, long src_n_stride,
                      int src_row_stride, int box_w, int box_h, int Wo, int Ho, int tmp_rows, const int32_t* xtab, int kx,
                      const int32_t* ytab, int ky, const int32_t* rows, hipStream_t stream);
+/* dsee_resample_u8 for a batch whose samples differ in source size (the files of a user's own folder): the same two passes, the
+ * same arithmetic and the same tables, one output size Wo x Ho for all N; only where a sample's source lies is given per sample.
+ * src is ONE uint8 arena of src_bytes bytes that holds the N sources (deepsee_amd/resample.py: pack_arena starts each on a
+ * 256-byte boundary); items is a device table int64 [N][4] of (byte offset of the box's first pixel inside the arena -- the centre
+ * crop folded in, like src_off --, row stride in bytes, box_w, box_h): offsets, never addresses.  xtab, ytab, rows, kx, ky, tmp
+ * [N][tmp_rows][Wo][C] and dst [N][Ho][Wo][C] are those of dsee_resample_u8, the tap counts padded to the batch maximum, tmp_rows
+ * the maximum of the samples' row counts and rows[2n + 1] <= box_h of sample n.  Table indices are clamped to each sample's own
+ * box; a sample whose box would reach past src_bytes (or whose item row is malformed) is skipped by both passes: nothing of it
+ * is read and its part of dst is left as it was. */
+int dsee_resample_u8_ragged(const uint8_t* src, long src_bytes, const int64_t* items, uint8_t* tmp, uint8_t* dst, int N, int C,
+                            int Wo, int Ho, int tmp_rows, const int32_t* xtab, int kx, const int32_t* ytab, int ky,
+                            const int32_t* rows, hipStream_t stream);
 /* F.interpolate(x, (S, S), mode) + clamp(-1, 1) of data/preprocessor.py:29-33 for the modes other than bicubic: mode 0 = bilinear
  * (align_corners=False, no antialias), 1 = nearest (floorf(dst * (float)in / out) capped at in - 1), 2 = area (adaptive average
  * over floor(i in / out) ... ceil((i + 1) in / out)).  NHWC [N][H][W][cs_in] -> [N][S][S][cs_out], 3 channels, like
